@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""bench.py - UHD (3840x2160) images/s of the Wave-Mamba forward on MI355X, with the HBM-roofline fraction of the
-hot-path operator that takes the most time (SURVEY.md 8d bytes) and the CPU-oracle network timed beside it.
+"""bench.py - UHD (3840x2160) images/s of the Wave-Mamba forward on MI355X; with --full also the HBM-roofline fraction of
+the hot-path operator that takes the most time (SURVEY.md 8d bytes) and the CPU-oracle network timed beside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's output when --dump-outputs is given, and
+prints the line (metric, value, unit, ms_per_step, dtype, ...).  Everything else - CPU baseline and parity, the
+instrumented roofline pass, the per-kernel table, the op-boundary, concurrent, bf16, graph and training legs - runs only
+with --full.
 
 A "step" = one forward of the shipped WaveMamba (inference_wavemamba.py:71-75 config, seeded random init -
 checkpoints are not distributed) over one synthetic 1x3x2160x3840 image, reflect-padded to 2176x3840 exactly as the
@@ -232,6 +237,32 @@ def self_launch(nproc, argv):
 
 def image_seed(rank):
     return 1234 + rank                                 # G(1234) on rank 0; every replica its own image
+
+
+DUMP_MAX_ELEMENTS = 1 << 23      # 32 MB of float32 per array: outputs above this are written as a fixed sample
+DUMP_SAMPLE_SEED = 5678
+
+
+def dump_outputs(out_dir, arrays):
+    """name -> tensor: each written as <out_dir>/<name>.npy in float32.  A tensor of more than DUMP_MAX_ELEMENTS elements is
+    written as <name>_sample.npy instead: the elements at DUMP_MAX_ELEMENTS flat positions drawn without replacement by a
+    generator seeded with DUMP_SAMPLE_SEED, in increasing position order - the same positions for the same shape on every
+    run.  -> {file name: what it holds}, for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        desc = {"shape": list(t.shape), "dtype": "float32"}
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMENTS].sort().values
+            desc["sample"] = (f"{DUMP_MAX_ELEMENTS} of {t.numel()} elements at flat positions randperm(seed "
+                              f"{DUMP_SAMPLE_SEED})[:{DUMP_MAX_ELEMENTS}], sorted")
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+        written[name + ".npy"] = desc
+    return written
 
 
 # ------------------------------------------------------------------------------------------------
@@ -521,13 +552,20 @@ def load_pmc(hp, wp):
         return None, None
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--width", type=int, default=3840)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32; "
+                         "the UHD output as a fixed seeded sample of 2^23 elements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: CPU baseline and parity, instrumented roofline pass, "
+                         "per-kernel table, op-boundary, concurrent, bf16, graph (--graph) and training legs.  The options "
+                         "below apply to --full runs only")
     ap.add_argument("--concurrent", type=int, default=4,
                     help="extra untimed leg at N = 1: throughput with this many forwards in flight on separate HIP "
                          "streams, no event instrumentation (0 = skip)")
@@ -545,7 +583,11 @@ def main():
     ap.add_argument("--train-steps", type=int, default=5)
     ap.add_argument("--no-bf16", action="store_true",
                     help="skip the bf16-storage leg (BASELINE config 2 as worded: bf16 planes between the kernels; rank 0, N = 1)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without an outer launcher: start the N ranks ourselves, exactly as the driver would
@@ -589,7 +631,7 @@ def main():
 
     # CPU baseline first (rank 0, N = 1 only), before the GPU pass: full UHD forwards
     cpu, y_cpu = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, y_cpu = cpu_baseline(x_cpu, args.cpu_forwards, args.cpu_budget)
 
     net = build_model(device)
@@ -608,23 +650,33 @@ def main():
                   "bars": {"rel_l2": 1e-4, "abs_dpsnr_db": 1e-3}}
         del yg, y_cpu
 
+    last = {}
+
     def step():
         with torch.no_grad():
             out = net.restoration_network(x)
-        return out[:, :, :args.height, :args.width]
+        out = out[:, :, :args.height, :args.width]
+        if args.dump_outputs:
+            last["output"] = out                       # what the caller of the timed path receives
+        return out
 
     sync = torch.cuda.synchronize
     barrier = dist.barrier if (world > 1 or rccl_selftest) else (lambda: None)
-    # `value` comes from an UN-instrumented pass: warm-up, then exactly K steps between barriers.  The roofline numbers come
-    # from a second pass of K steps with HIP events around the launches of the selective-scan op (~10 us of stream time per
+    # `value` comes from an UN-instrumented pass: warm-up, then exactly K steps between barriers.  The roofline numbers (--full)
+    # come from a second pass of K steps with HIP events around the launches of the selective-scan op (~10 us of stream time per
     # instrumented launch, 42 per step) - its wall time is reported next to it, never as `value`.
     elapsed = timed_steps(step, args.steps, max(args.warmup, 1), sync, barrier)
-    wm.ops.prof_enable(CORE_CLASSES)
-    elapsed_instr = timed_steps(step, args.steps, 0, sync, barrier)
-    prof = {k: v for k, v in wm.ops.prof_collect().items() if k in CORE_CLASSES}
-    prof_steps = {k: args.steps for k in prof}
-    iso = {}
-    if rank == 0 and not args.timed_only:
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last)
+    last.clear()
+    prof, prof_steps, iso, elapsed_instr = {}, {}, {}, None
+    if args.full:
+        wm.ops.prof_enable(CORE_CLASSES)
+        elapsed_instr = timed_steps(step, args.steps, 0, sync, barrier)
+        prof = {k: v for k, v in wm.ops.prof_collect().items() if k in CORE_CLASSES}
+        prof_steps = {k: args.steps for k in prof}
+    if args.full and rank == 0 and not args.timed_only:
         # the untimed pass runs the single-stream order: every launch alone on the GPU (in the timed region the down
         # path's high-frequency branches run on side streams under the main stream's kernels, which lengthens both)
         extra = max(2, min(args.steps, 5))
@@ -641,10 +693,11 @@ def main():
             elif k in CORE_CLASSES and v[0]:
                 iso[k] = v[1] / extra
         unet.two_streams = two
-    wm.ops.prof_enable(False)
+    if args.full:
+        wm.ops.prof_enable(False)
 
     concurrent = None
-    if rank == 0 and world == 1 and args.concurrent > 1 and not args.timed_only:
+    if args.full and rank == 0 and world == 1 and args.concurrent > 1 and not args.timed_only:
         cs = [torch.cuda.Stream(device) for _ in range(args.concurrent)]
 
         def cstep(i):
@@ -662,30 +715,30 @@ def main():
         concurrent = {"streams": len(cs), "steps": kc, "images_per_s": kc / ce, "ms_per_image": 1e3 * ce / kc,
                       "note": "same forward, steps round-robin over the streams (that many images in flight), no HIP-event "
                               "instrumentation; serving throughput, not the contract's `value`"}
-    op_boundary = scan_op_boundary(device, hp, wp) if rank == 0 and not args.timed_only else None
-    hip_graph = graph_replay(step, args.steps, device) if rank == 0 and world == 1 and args.graph else None
+    op_boundary = scan_op_boundary(device, hp, wp) if args.full and rank == 0 and not args.timed_only else None
+    hip_graph = graph_replay(step, args.steps, device) if args.full and rank == 0 and world == 1 and args.graph else None
     bf16 = None
-    if rank == 0 and world == 1 and not args.no_bf16 and not args.timed_only:
+    if args.full and rank == 0 and world == 1 and not args.no_bf16 and not args.timed_only:
         try:
             from wave_mamba_amd import inference
             bf16 = inference.bench_bf16_storage(net, x, args.steps)
         except Exception as e:
             bf16 = {"error": f"{type(e).__name__}: {e}"[:300]}
     train = None
-    if rank == 0 and world == 1 and not args.no_train and not args.timed_only:
+    if args.full and rank == 0 and world == 1 and not args.no_train and not args.timed_only:
         try:
             train = train_leg(device, args.train_steps, with_cpu_loss=not args.no_cpu_baseline)
         except Exception as e:
             train = {"error": f"{type(e).__name__}: {e}"[:300]}
     ddp = None
-    if (world > 1 or rccl_selftest) and not args.no_train and not args.timed_only:
+    if args.full and (world > 1 or rccl_selftest) and not args.no_train and not args.timed_only:
         try:
             ddp = ddp_train_leg(device, rank, world, args.train_steps, "cpu" if share else device)
         except Exception as e:
             ddp = {"error": f"{type(e).__name__}: {e}"[:300]}
     elapsed = max_over_ranks(elapsed, world, "cpu" if share else device)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         pos = scan_positions(hp, wp)                       # positions scanned per image (14 LFSSBlocks)
         haar_b = 2 * 4 * 32 * hp * wp * (1 + 1 / 4 + 1 / 16)          # 2*e*B*C*H*W per level
         table = {}
@@ -775,6 +828,15 @@ def main():
                    "achieved_GBps": hot_bytes / (hot_iso_ms * 1e-3) / 1e9 if hot_iso_ms else None,
                    "frac": hot_bytes / (hot_iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if hot_iso_ms else None,
                    "ceiling_images_per_s": HBM_PEAK_GBS * 1e9 / hot_bytes}
+        full_fields = {
+            "roofline": roof, "cpu_baseline": cpu, "parity": parity,
+            "roofline_table": table,
+            "hot_path_ms_per_step": sum(table[k]["ms_per_step"] for k in table if k in hot_names),
+            "hot_path_sum": hot_sum,
+            "selscan_op_boundary": op_boundary, "hip_graph_replay": hip_graph, "bf16_storage": bf16,
+            "concurrent_forwards": concurrent, "training_config3_one_gpu": train, "training_config3_ddp": ddp,
+        }
+    if rank == 0:
         line = {
             "metric": "UHD (3840x2160) images/sec fwd", "value": whole_job_value(world, args.steps, 1, elapsed),
             "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -786,13 +848,11 @@ def main():
                                    f"its down-path high-frequency branches on side streams: "
                                    f"{bool(getattr(net.restoration_network, 'two_streams', False))}"},
             "ranks": ranks_info,
-            "roofline": roof, "cpu_baseline": cpu, "parity": parity,
-            "roofline_table": table,
-            "hot_path_ms_per_step": sum(table[k]["ms_per_step"] for k in table if k in hot_names),
-            "hot_path_sum": hot_sum,
-            "selscan_op_boundary": op_boundary, "hip_graph_replay": hip_graph, "bf16_storage": bf16,
-            "concurrent_forwards": concurrent, "training_config3_one_gpu": train, "training_config3_ddp": ddp,
         }
+        if args.full:
+            line.update(full_fields)
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -1,13 +1,13 @@
-"""Drop-in proof (build container only: needs /root/reference at run time, nothing of it is stored in the repo).
+"""Drop-in proof: the arch file works inside a `basicsr` package laid out like the reference's.
 
-A temporary `basicsr/` package is assembled from the reference's REAL `utils/registry.py` and REAL `archs/__init__.py`
-(copied into a temp dir at test time), a two-function stand-in for `basicsr.utils` (the real one imports cv2, which this
-image lacks), and THIS repo's `archs/wavemamba_arch.py` copied into `basicsr/archs/`.  Then exactly what the reference's
-callers do: the `*_arch.py` auto-scan (archs/__init__.py:12-16), `build_network({'type': 'WaveMamba', ...})`
-(:19-25), `load_state_dict(torch.load(path)['params'], strict=False)` (inference_wavemamba.py:77), a forward.
+A temporary `basicsr/` package is assembled at test time: `utils/registry.py` is this repo's `wave_mamba_amd/registry.py`
+(the surface of basicsr's Registry, uniqueness assertion included), `archs/__init__.py` is a stand-in written below with
+what basicsr's does (import every `*_arch.py` of the folder as `basicsr.archs.<name>`, `build_network(opt)` pops 'type' and
+instantiates from `ARCH_REGISTRY`), `utils/__init__.py` is empty, and THIS repo's `archs/wavemamba_arch.py` is copied into
+`basicsr/archs/`.  Then exactly what the reference's callers do: the auto-scan, `build_network({'type': 'WaveMamba', ...})`,
+`load_state_dict(torch.load(path)['params'], strict=False)` (inference_wavemamba.py:77), a forward.
 """
 import importlib
-import logging
 import os
 import shutil
 import sys
@@ -15,11 +15,20 @@ import sys
 import pytest
 import torch
 
-REF = "/root/reference/basicsr"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = dict(in_chn=3, wf=8, n_l_blocks=[1, 1, 1], n_h_blocks=[1, 1, 1], ffn_scale=2.0)
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
+# basicsr/archs/__init__.py: the *_arch.py auto-scan and build_network
+ARCHS_INIT = (
+    "import importlib\n"
+    "import os\n"
+    "from basicsr.utils.registry import ARCH_REGISTRY\n"
+    "_here = os.path.dirname(os.path.abspath(__file__))\n"
+    "_arch_modules = [importlib.import_module('basicsr.archs.' + f[:-3])\n"
+    "                 for f in sorted(os.listdir(_here)) if f.endswith('_arch.py')]\n"
+    "def build_network(opt):\n"
+    "    opt = dict(opt)\n"
+    "    return ARCH_REGISTRY.get(opt.pop('type'))(**opt)\n")
 
 
 @pytest.fixture()
@@ -28,15 +37,9 @@ def basicsr_tree(tmp_path):
     (pkg / "utils").mkdir(parents=True)
     (pkg / "archs").mkdir()
     (pkg / "__init__.py").write_text("")
-    # stand-in for basicsr/utils/__init__.py: the two names archs/__init__.py imports (:5)
-    (pkg / "utils" / "__init__.py").write_text(
-        "import logging, os\n"
-        "def get_root_logger(*a, **k):\n    return logging.getLogger('basicsr')\n"
-        "def scandir(dir_path, suffix=None, recursive=False, full_path=False):\n"
-        "    for e in os.scandir(dir_path):\n"
-        "        if e.is_file() and not e.name.startswith('.'):\n            yield e.name\n")
-    shutil.copy(os.path.join(REF, "utils", "registry.py"), pkg / "utils" / "registry.py")      # the real registry
-    shutil.copy(os.path.join(REF, "archs", "__init__.py"), pkg / "archs" / "__init__.py")      # the real auto-scan
+    (pkg / "utils" / "__init__.py").write_text("")
+    shutil.copy(os.path.join(ROOT, "wave_mamba_amd", "registry.py"), pkg / "utils" / "registry.py")
+    (pkg / "archs" / "__init__.py").write_text(ARCHS_INIT)
     shutil.copy(os.path.join(ROOT, "wave_mamba_amd", "archs", "wavemamba_arch.py"), pkg / "archs" / "wavemamba_arch.py")
     saved = {k: v for k, v in sys.modules.items() if k == "basicsr" or k.startswith("basicsr.")}
     for k in saved:
@@ -63,7 +66,7 @@ def test_arch_file_drops_into_basicsr(basicsr_tree, tmp_path):
     assert dropped._hip_ops is wm.ops                             # operators come from the installed package
 
     torch.manual_seed(0)
-    net = archs.build_network(dict(type="WaveMamba", **CFG))      # archs/__init__.py:19-25
+    net = archs.build_network(dict(type="WaveMamba", **CFG))
     assert isinstance(net, torch.nn.Module) and hasattr(net, "restoration_network")
     for name in ("forward", "test", "test_tile", "check_image_size", "encode_and_decode", "print_network"):
         assert callable(getattr(net, name)), name
@@ -96,4 +99,4 @@ def test_registering_twice_is_rejected_like_the_reference(basicsr_tree):
     importlib.import_module("basicsr.archs")
     reg = importlib.import_module("basicsr.utils.registry").ARCH_REGISTRY
     with pytest.raises(AssertionError):
-        reg.register(sys.modules["basicsr.archs.wavemamba_arch"].WaveMamba)      # registry.py:38-41
+        reg.register(sys.modules["basicsr.archs.wavemamba_arch"].WaveMamba)      # Registry._do_register's assertion

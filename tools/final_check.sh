@@ -8,7 +8,7 @@ timeout 2400 bash tools/profile_round.sh > $O/profile_round.log 2>&1; head -3 $O
 cp gpurun_out/prof_round/pmc_traffic.json profiles/pmc_traffic.json 2>/dev/null
 timeout 900 bash tools/pmc_step_all.sh > $O/pmc_step_all.log 2>&1; tail -5 $O/pmc_step_all.log
 timeout 600 python tools/host_bound.py > $O/host_bound.txt 2>&1; head -12 $O/host_bound.txt
-timeout 1500 python bench.py 2> $O/bench_default.err | grep '^{' > $O/bench_default.json
+timeout 1500 python bench.py --full 2> $O/bench_default.err | grep '^{' > $O/bench_default.json
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/final/bench_default.json"))

@@ -9,7 +9,7 @@ rows = rows[:idx[0]] if idx else rows              # drop the op-boundary scan l
 ha = [i for i, r in enumerate(rows) if 'haar_analysis' in r['Kernel_Name']]
 starts = ha[0::3]
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-# `bench.py --steps 5 --warmup 3 --timed-only`: 3 warm-up + 5 timed forwards; use timed steps 2..4 (the last one has no
+# `bench.py --full --steps 5 --warmup 3 --timed-only`: 3 warm-up + 5 timed forwards; use timed steps 2..4 (the last one has no
 # successor to delimit it)
 s0, s1 = starts[3 + 1], starts[3 + 1 + n]
 step = rows[s0:s1]
@@ -23,7 +23,7 @@ for r in step:
     agg[r['Kernel_Name']][0] += 1; agg[r['Kernel_Name']][1] += dur(r)
 tot = sum(v[1] for v in agg.values()); wmt = sum(v[1] for k, v in agg.items() if 'wm::' in k)
 wall = (int(rows[s1]['Start_Timestamp']) - int(rows[s0]['Start_Timestamp'])) / n / 1e6
-print(f"# per-step kernel time, mean of {n} timed steps of `rocprofv3 --kernel-trace -- python bench.py --steps 5 --warmup 3 --no-cpu-baseline --timed-only`")
+print(f"# per-step kernel time, mean of {n} timed steps of `rocprofv3 --kernel-trace -- python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --timed-only`")
 print(f"# step wall {wall:.2f} ms; sum of kernel durations {tot / n / 1e6:.2f} ms/step in {len(step) / n:.0f} dispatches (kernels of the side "
       f"streams overlap the main stream's: the sum exceeds the wall, and a kernel sharing the GPU runs longer than alone); "
       f"wm:: kernels {wmt / n / 1e6:.2f} ms/step")
