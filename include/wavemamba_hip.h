@@ -356,6 +356,25 @@ int wm_conv2d_wgrad(const float* gy, const float* x, float* dW, float* db, void*
 int wm_l1_mean_fwd(const float* a, const float* b, float* out, int64_t n, void* stream);
 int wm_l1_mean_bwd(const float* a, const float* b, const float* gout, float* ga, int64_t n, void* stream);
 
+/* Image-quality metrics of the reference's evaluation loop (inference_wavemamba.py:116-117, :133-134 -> comput_psnr_ssim.py with
+ * crop_border, input_order 'HWC' / 'CHW', test_y_channel = True), csrc/metrics.hip.h.
+ *   Images: N uint8 images of H x W x 3, element (n, h, w, ch) at n sn + h sh + w sw + ch sc (strides in elements, >= 0: HWC and
+ *   CHW alike); bgr = 1: channel 0 is blue (cv2.imread / tensor2img), bgr = 0: channel 0 is red.  a and b share the strides.
+ *   Y (to_y_channel :374-385 -> bgr2ycbcr :210-237, bit for bit): x = float32(u8) / 255 in float32,
+ *     y64 = ((x_b 24.966 + x_g 128.553) + x_r 65.481) + 16 in float64, Y = float32(float32(y64 / 255) * 255).
+ *   wm_psnr_ssim_y_u8: crop [crop, H - crop) x [crop, W - crop) (:426-428, :642-644; crop 0 = none), then per image
+ *     out[2 n] = PSNR = 20 log10(255 / sqrt(mse)) (:430-438; +inf when mse = 0; mse in float64 - the reference's is float32),
+ *     out[2 n + 1] = SSIM = mean of _ssim_cly's map (:558-593: 11 x 11 Gaussian of sigma 1.5, BORDER_REPLICATE, float64).
+ *     out: N x 2 doubles, 8-byte aligned.  workspace: wm_psnr_ssim_y_workspace_bytes(N, H, W, crop) bytes, 8-byte aligned; every
+ *     byte of it that is read is written first in the same call (nothing needs zeroing).  Deterministic (fixed summation order, no
+ *     atomics).  WM_EINVAL when crop < 0 or crop >= min(H, W) / 2 (nothing left to measure); workspace_bytes is then 0.
+ *   wm_y_channel_u8: y (N, H, W) float32 dense = Y of every pixel (no crop). */
+size_t wm_psnr_ssim_y_workspace_bytes(int N, int H, int W, int crop);
+int wm_psnr_ssim_y_u8(const uint8_t* a, const uint8_t* b, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W,
+                      int crop, int bgr, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int wm_y_channel_u8(const uint8_t* img, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W, int bgr, float* y,
+                    void* stream);
+
 /* sums (C) = sum over batch and plane of x (B, C, H, W): the bias gradient of a convolution (training). */
 int wm_plane_sums(const float* x, float* sums, int B, int C, int H, int W, void* stream);
 

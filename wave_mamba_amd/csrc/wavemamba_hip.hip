@@ -30,6 +30,7 @@
 #include "conv_wgrad.hip.h"
 #include "patchify.hip.h"
 #include "loss.hip.h"
+#include "metrics.hip.h"
 
 namespace wm {
 
@@ -254,7 +255,7 @@ using namespace wm;
 // ================================================================================================
 extern "C" {
 
-int wm_abi_version(void) { return 31; }
+int wm_abi_version(void) { return 32; }
 
 #ifndef WM_BUILD_ID
 #define WM_BUILD_ID "unknown"
@@ -2142,6 +2143,75 @@ int wm_event_synchronize_relaxed(void* event) {
     const hipError_t e = hipEventSynchronize(static_cast<hipEvent_t>(event));
     hipThreadExchangeStreamCaptureMode(&mode);
     return e == hipSuccess ? WM_OK : WM_EHIP;
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// Image-quality metrics (csrc/metrics.hip.h): Y-channel PSNR / SSIM of uint8 image pairs, and the Y plane alone
+// ================================================================================================
+static bool met_image(MetImage& im, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int bgr) {
+    if (sn < 0 || sh < 0 || sw < 0 || sc < 0) return false;
+    im = MetImage{(long long)sn, (long long)sh, (long long)sw, (long long)sc, bgr ? 0 : 2, bgr ? 2 : 0};
+    return true;
+}
+
+static bool met_window(int N, int H, int W, int crop, int& Hc, int& Wc) {
+    if (N < 1 || H < 1 || W < 1 || crop < 0 || N > 65535) return false;
+    Hc = H - 2 * crop;
+    Wc = W - 2 * crop;
+    return Hc >= 1 && Wc >= 1;                         // crop >= min(H, W) / 2 leaves nothing to measure
+}
+
+extern "C" {
+
+size_t wm_psnr_ssim_y_workspace_bytes(int N, int H, int W, int crop) {
+    int Hc, Wc;
+    if (!met_window(N, H, W, crop, Hc, Wc)) return 0;
+    const size_t tiles = (size_t)((Wc + MET_TW - 1) / MET_TW) * (size_t)((Hc + MET_TH - 1) / MET_TH);
+    return (size_t)N * tiles * 2 * sizeof(double);
+}
+
+int wm_psnr_ssim_y_u8(const uint8_t* a, const uint8_t* b, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W,
+                      int crop, int bgr, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    int Hc, Wc;
+    MetImage im;
+    if (!met_window(N, H, W, crop, Hc, Wc) || !met_image(im, sn, sh, sw, sc, bgr)) return WM_EINVAL;
+    if (!a || !b || !out || !workspace) return WM_ENULL;
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) return WM_EALIGN;
+    if (workspace_bytes < wm_psnr_ssim_y_workspace_bytes(N, H, W, crop)) return WM_EWORKSPACE;
+    MetGauss gw;                                           // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 1.5^2)), normalised
+    double sum = 0.0;
+    for (int i = 0; i < MET_TAPS; ++i) {
+        const double x = i - (MET_TAPS - 1) * 0.5;
+        gw.g[i] = exp(-0.5 / (1.5 * 1.5) * x * x);
+        sum += gw.g[i];
+    }
+    for (int i = 0; i < MET_TAPS; ++i) gw.g[i] *= 1.0 / sum;
+    const int tx = (Wc + MET_TW - 1) / MET_TW, ty = (Hc + MET_TH - 1) / MET_TH;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(psnr_ssim_tile_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)N), dim3(256), 0, st, a, b, im, crop, Hc, Wc,
+                       gw, part);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(psnr_ssim_finish_kernel, dim3((unsigned)N), dim3(256), 0, st, (const double*)part, tx * ty, (double)Hc * Wc,
+                       out);
+    return launch_status();
+}
+
+int wm_y_channel_u8(const uint8_t* img, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W, int bgr, float* y,
+                    void* stream) {
+    int Hc, Wc;
+    MetImage im;
+    if (!met_window(N, H, W, 0, Hc, Wc) || !met_image(im, sn, sh, sw, sc, bgr)) return WM_EINVAL;
+    if (!img || !y) return WM_ENULL;
+    if (reinterpret_cast<uintptr_t>(y) & 3u) return WM_EALIGN;
+    const long long total = (long long)N * H * W;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(y_channel_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, im, H, W, total, y);
+    return launch_status();
 }
 
 }  // extern "C"

@@ -987,6 +987,65 @@ def image_post_u8(t, h, w, swap_rb=True):
     return out
 
 
+def _metric_images(name, layout, *imgs):
+    """uint8 CUDA images (H, W, 3) / (N, H, W, 3) for layout 'HWC', (3, H, W) / (N, 3, H, W) for 'CHW', all of one shape and
+    device -> (4-D views, N, H, W, element strides (n, h, w, channel) shared by all of them)."""
+    if layout not in ("HWC", "CHW"):
+        raise ValueError(f"{name}: layout must be 'HWC' or 'CHW', got {layout!r}")
+    _require_cuda(name, *imgs)
+    for t in imgs:
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"{name}: expected uint8 images, got {t.dtype}")
+        if t.shape != imgs[0].shape:
+            raise RuntimeError(f"{name}: image shapes differ: {tuple(imgs[0].shape)} vs {tuple(t.shape)}")
+        if t.device != imgs[0].device:
+            raise RuntimeError(f"{name}: images on different devices: {imgs[0].device} vs {t.device}")
+    ch = 3 if layout == "HWC" else 1
+    if imgs[0].dim() not in (3, 4) or imgs[0].shape[ch - 4] != 3:
+        raise RuntimeError(f"{name}: expected {'(N, H, W, 3)' if layout == 'HWC' else '(N, 3, H, W)'} images, got {tuple(imgs[0].shape)}")
+    v = [t if t.dim() == 4 else t.unsqueeze(0) for t in imgs]
+    if any(t.stride() != v[0].stride() for t in v):
+        v = [t.contiguous() for t in v]
+    s = v[0].stride()
+    if layout == "HWC":
+        N, H, W, _ = v[0].shape
+        strides = (s[0], s[1], s[2], s[3])
+    else:
+        N, _, H, W = v[0].shape
+        strides = (s[0], s[2], s[3], s[1])
+    return v, N, H, W, strides
+
+
+def psnr_ssim_y(a, b, crop_border=1, layout="HWC", bgr=True):
+    """Y-channel PSNR and SSIM of uint8 CUDA image pairs on the device (comput_psnr_ssim.calculate_psnr / calculate_ssim with
+    test_y_channel=True, as inference_wavemamba.py:116-117 calls them; definition in include/wavemamba_hip.h).
+    a, b: (N, H, W, 3) for layout 'HWC' or (N, 3, H, W) for 'CHW' (or one image without N); bgr: channel 0 is blue.
+    -> (N, 2) float64 CUDA tensor of (PSNR in dB, SSIM) per image; PSNR is inf for identical Y planes.  No host synchronisation."""
+    lib = _lib.load()
+    (va, vb), N, H, W, st = _metric_images("psnr_ssim_y", layout, a, b)
+    crop = int(crop_border)
+    ws_bytes = lib.wm_psnr_ssim_y_workspace_bytes(N, H, W, crop)
+    if ws_bytes == 0:
+        raise RuntimeError(f"psnr_ssim_y: crop_border {crop} leaves nothing of a {H} x {W} image (needs 0 <= crop < min(H, W) / 2)")
+    out = torch.empty((N, 2), dtype=torch.float64, device=va.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=va.device)
+    with torch.cuda.device(va.device):
+        check(lib.wm_psnr_ssim_y_u8(_ptr(va), _ptr(vb), *st, N, H, W, crop, int(bool(bgr)), _ptr(out), _ptr(ws), ws_bytes,
+                                    _stream()), "wm_psnr_ssim_y_u8")
+    return out
+
+
+def y_channel_u8(img, layout="HWC", bgr=True):
+    """The reference's to_y_channel (comput_psnr_ssim.py:374-385, BT.601 Y in [16, 235], bit for bit) of uint8 CUDA images:
+    (N, H, W, 3) / (N, 3, H, W) -> (N, H, W) float32, or (H, W) for one image without N."""
+    lib = _lib.load()
+    (v,), N, H, W, st = _metric_images("y_channel_u8", layout, img)
+    y = torch.empty((N, H, W), dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        check(lib.wm_y_channel_u8(_ptr(v), *st, N, H, W, int(bool(bgr)), _ptr(y), _stream()), "wm_y_channel_u8")
+    return y if img.dim() == 4 else y[0]
+
+
 def match_index(G, nx, ny):
     """Channel matching with every channel kept: (B, C) int32 index of the L2-nearest candidate channel from the
     Gram outputs of `gram(maps, candidates)` (argmin_j |x_c|^2 + |y_j|^2 - 2 x_c . y_j)."""
