@@ -102,7 +102,7 @@ DW_SHAPES = [
 @pytest.mark.parametrize("shape", DW_SHAPES)
 @pytest.mark.parametrize("act", ["none", "silu", "gelu"])
 def test_dwconv3x3_bf16_is_the_rounded_fp32_form(shape, act):
-    """Each dispatch form of dwconv3x3_kernel<ACT, VEC, bf16_t, LPR> (wavemamba_hip.hip: dw_lanes_per_row), with and without
+    """Each dispatch form of dwconv3x3_kernel<ACT, VEC, bf16_t, LPR> (csrc/lfss.hip: dw_lanes_per_row), with and without
     bias, plain and flipped taps (act + 4)."""
     B, C, H, W = shape
     g = gen(B * 7919 + C * 131 + H * 17 + W)
@@ -153,7 +153,7 @@ def test_dwconv3x3_bf16_inf_and_nan(W):
                                    (1, 65541, 5, 7)])      # element-wise form: one plane per group, 65541 groups
 def test_dwconv3x3_past_the_grid_z_cap(shape):
     """wm_dwconv3x3_fwd and wm_dwconv3x3_wgrad launch at most 65535 plane groups in grid z and loop over the rest
-    (wavemamba_hip.hip: `pgroups < 65535 ? pgroups : 65535`): forward (fp32 and bf16), input gradient and weight / bias
+    (csrc/lfss.hip: `pgroups < 65535 ? pgroups : 65535`): forward (fp32 and bf16), input gradient and weight / bias
     gradient past the cap, against float64."""
     B, C, H, W = shape
     g = torch.Generator(device=DEV); g.manual_seed(C)

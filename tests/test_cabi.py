@@ -143,7 +143,11 @@ def test_library_isa_has_no_scalar_source_packed_f32_with_routed_halves():
     assert [h[1].split()[1] for h in hits] == ["v[42:43],", "v[50:51],", "v[6:7],", "v[10:11],"], hits
     if not os.path.exists(os.path.join(lint.LLVM, "llvm-objdump")):
         pytest.skip("llvm-objdump not available")
-    bad = lint.offending(lint.disassemble(_lib.LIB_PATH))
+    from wave_mamba_amd import build
+    texts = lint.disassemble_all(_lib.LIB_PATH)             # one device code object per translation unit: all of them are read
+    print(f"ISA lint: {len(texts)} device code objects in {_lib.LIB_PATH}")
+    assert len(texts) == len(build.units()), (len(texts), build.units())
+    bad = [b for t in texts for b in lint.offending(t)]
     assert not bad, f"{len(bad)} packed-fp32 instruction(s) with unsafe op_sel routing, first: {bad[0]}"
 
 

@@ -2894,3 +2894,30 @@ def test_scale_add_vs_fp64_autograd(shape):
     assert_close(out.detach(), ref.detach().float(), 1e-6, "scale_add")
     assert_close(gx, rx.float(), 1e-6, "scale_add d/dx"); assert_close(go, ro.float(), 1e-6, "scale_add d/do")
     assert_close(gs, rs.float(), 2e-5, "scale_add d/dscale")       # a sum of B H W products of both signs, fp32 accumulation
+
+
+def test_prof_counts_launches_of_every_translation_unit():
+    """The profiling hooks are one process-wide object (csrc/common.hip: g_prof) that the launch code of every translation unit
+    records into: with every class enabled, a tiny WaveMamba forward is counted in classes launched from four different units
+    (haar_image.hip, scan_fwd.hip, lfss.hip, conv.hip), and prof_enable(False) stops the counting.  A per-unit copy of the state
+    would show wm_prof_collect (common.hip) none of these launches."""
+    torch.manual_seed(0)
+    net = wm.WaveMamba(in_chn=3, wf=16, n_l_blocks=[1, 1, 2], n_h_blocks=[1, 1, 1], ffn_scale=2.0).eval().to(DEV)
+    img = torch.rand(1, 3, 64, 96, device=DEV)
+    wm.ops.prof_enable(True)
+    try:
+        with torch.no_grad():
+            net(img)
+        torch.cuda.synchronize()
+        on = wm.ops.prof_collect()
+    finally:
+        wm.ops.prof_enable(False)
+    print({k: v[0] for k, v in on.items() if v[0]})
+    for name in ("haar_analysis", "ss2d_core_scan", "lfss_mid", "conv3x3"):
+        assert on[name][0] > 0, (name, on)
+        assert on[name][1] > 0.0, (name, on)
+    with torch.no_grad():
+        net(img)
+    torch.cuda.synchronize()
+    off = wm.ops.prof_collect()
+    assert {k: v[0] for k, v in off.items()} == {k: v[0] for k, v in on.items()}

@@ -1,14 +1,14 @@
 #!/bin/bash
 # tools/build_variant.sh NAME [hipcc flags...]  ->  build/variants/NAME.so  (A/B builds: WAVEMAMBA_HIP_LIB=build/variants/NAME.so)
-# The library's own flags (wave_mamba_amd/build.py: HIPCC_FLAGS, incl. -fno-slp-vectorize) + the extra ones; "-slp" as an extra flag
-# drops -fno-slp-vectorize (the round-4 code generator).
+# wave_mamba_amd/build.py: build_variant() with the library's own flags + the extra ones; "-slp" as an extra flag drops
+# -fno-slp-vectorize (the round-4 code generator, which the ISA lint refuses: that variant is linked without the lint).
 set -e
 cd "$(dirname "$0")/.."
-name=$1; shift
-mkdir -p build/variants
-id=$(python -c "import sys; sys.path.insert(0, '.'); from wave_mamba_amd import build; print(build.source_id())")
-flags=$(python -c "import sys; sys.path.insert(0, '.'); from wave_mamba_amd import build; print(' '.join(build.HIPCC_FLAGS))")
-extra=()
-for a in "$@"; do if [ "$a" = "-slp" ]; then flags=${flags/-fno-slp-vectorize/}; else extra+=("$a"); fi; done
-/opt/rocm/bin/hipcc $flags "-DWM_BUILD_ID=\"$id+$name\"" "${extra[@]}" wave_mamba_amd/csrc/wavemamba_hip.hip -o build/variants/$name.so
-echo "built build/variants/$name.so ($*)"
+python -c "
+import sys; sys.path.insert(0, '.')
+from wave_mamba_amd import build
+name, extra = sys.argv[1], sys.argv[2:]
+slp = '-slp' in extra
+build.build_variant('build/variants/%s.so' % name, extra_flags=[f for f in extra if f != '-slp'],
+                    drop_flags=['-fno-slp-vectorize'] if slp else [], id_suffix=name, check=not slp, verbose=True)
+print('built build/variants/%s.so (%s)' % (name, ' '.join(extra)))" "$@"

@@ -1,18 +1,18 @@
 #!/usr/bin/env python3
-"""Which kernels wait out their global loads one at a time?  Compiles the library with -save-temps and, per kernel, counts
-global / buffer loads and `s_waitcnt vmcnt(0)` instructions: a ratio near 1 means load - full wait - load - full wait
-(the `cond ? load : 0` pattern: a branch around each load and a wait behind it).
+"""Which kernels wait out their global loads one at a time?  Compiles every unit of the library to assembly (build.build_variant)
+and, per kernel, counts global / buffer loads and `s_waitcnt vmcnt(0)` instructions: a ratio near 1 means load - full wait -
+load - full wait (the `cond ? load : 0` pattern: a branch around each load and a wait behind it).
 
 usage: python tools/isa_load_waits.py [min-loads]"""
-import re, sys, subprocess, os, tempfile
+import re, sys, subprocess, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-tmp = tempfile.mkdtemp()
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
-                "-save-temps=obj", os.path.join(root, "wave_mamba_amd/csrc/wavemamba_hip.hip"), "-o", os.path.join(tmp, "t.so")],
-               cwd=tmp, capture_output=True)
-asm = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f][0]
+sys.path.insert(0, root)
+from wave_mamba_amd import build
+out = os.path.join(root, "build", "asm")
+build.build_variant(out, asm=True)
+asm_lines = [ln for u in build.units() for ln in open(os.path.join(out, u + ".s"))]
 cur, stats = None, {}
-for ln in open(os.path.join(tmp, asm)):
+for ln in asm_lines:
     m = re.match(r"^(_Z\w+):", ln)
     if m:
         cur = m.group(1); stats[cur] = [0, 0]; continue

@@ -2,7 +2,7 @@
 """VALU issue cycles of the innermost (scan-step) loops of the selective-scan kernels, counted from the ISA (VERDICT r4 item 2:
 "count the issue cycles from the ISA, do not estimate").
 
-usage: python tools/isa_valu_count.py [file.s]      (default: compiles csrc/wavemamba_hip.hip -S with the library's flags)
+usage: python tools/isa_valu_count.py [file.s]      (default: compiles csrc/scan_fwd.hip -S with the library's flags)
 
 Per kernel instantiation and per innermost loop (the `for q` loop of core_body: FOUR scan steps per iteration): instructions by
 class and the issue cycles they cost one wave on its SIMD (gfx950, tools/microbench + ubench_mfma_valu: a VALU instruction of
@@ -22,10 +22,9 @@ def isa(path=None):
         return open(path).read()
     sys.path.insert(0, ROOT)
     from wave_mamba_amd import build
-    flags = [f for f in build.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    out = "/tmp/wm_isa_count.s"
-    subprocess.run([build.hipcc_path()] + flags + ["-S", "--cuda-device-only", "-o", out, build.SRC], check=True, capture_output=True)
-    return open(out).read()
+    out = os.path.join(ROOT, "build", "asm")
+    build.build_variant(out, asm=True, only=["scan_fwd"])
+    return open(os.path.join(out, "scan_fwd.s")).read()
 
 
 def kernels(text, pattern):

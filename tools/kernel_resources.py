@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""Per-kernel register / scratch / LDS usage of the library (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
+"""Per-kernel register / scratch / LDS usage of the library (hipcc -Rpass-analysis=kernel-resource-usage over every unit, with the
+library's own flags: wave_mamba_amd/build.py build_variant), one line each.
 
 usage: python tools/kernel_resources.py [substring-of-demangled-name] [extra hipcc flags ...]
 """
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, root)
+from wave_mamba_amd import build
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
-       "-Rpass-analysis=kernel-resource-usage", os.path.join(root, "wave_mamba_amd/csrc/wavemamba_hip.hip"),
-       "-o", "/tmp/_kres.so"] + sys.argv[2:]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+err = "".join(build.build_variant(os.path.join(root, "build", "asm_resources"), asm=True, force=True,
+                                  extra_flags=["-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]).values())
 cur = None
 rows = {}
 for line in err.splitlines():

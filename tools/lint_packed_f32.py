@@ -8,7 +8,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from wave_mamba_amd._lint_packed_f32 import *          # noqa: F401,F403
-from wave_mamba_amd._lint_packed_f32 import main, LLVM, disassemble, offending      # noqa: F401
+from wave_mamba_amd._lint_packed_f32 import main, LLVM, disassemble, disassemble_all, offending      # noqa: F401
 
 if __name__ == "__main__":
     sys.exit(main())

@@ -31,18 +31,25 @@ SEL = re.compile(r"op_sel:\[([01,]+)\]")
 SELHI = re.compile(r"op_sel_hi:\[([01,]+)\]")
 
 
-def disassemble(lib):
+def disassemble_all(lib):
+    """-> the disassembly of every device code object in the library, one text each (the library carries one per translation unit)"""
     tmp = tempfile.mkdtemp(prefix="wm_lint_")
     try:
         local = os.path.join(tmp, "lib.so")
         shutil.copy(lib, local)
         subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], check=True, capture_output=True, cwd=tmp)
-        objs = [p for p in glob.glob(local + ".*") if "amdgcn" in p]
+        objs = sorted(p for p in glob.glob(local + ".*") if "amdgcn" in p)
         if not objs:
             raise RuntimeError("no device code object in " + lib)
-        return subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", objs[0]], check=True, capture_output=True, text=True).stdout
+        return [subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", o], check=True, capture_output=True, text=True).stdout
+                for o in objs]
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+def disassemble(lib):
+    """-> one text: all of disassemble_all(lib)"""
+    return "\n".join(disassemble_all(lib))
 
 
 def offending(text):
@@ -72,10 +79,11 @@ def offending(text):
 
 def main():
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "libwavemamba_hip.so")
-    bad = offending(disassemble(lib))
+    texts = disassemble_all(lib)
+    bad = [b for t in texts for b in offending(t)]
     for sym, ins in bad[:40]:
         print(f"{sym}: {ins}")
-    print(f"{len(bad)} packed-fp32 instruction(s) with unsafe op_sel routing in {lib}")
+    print(f"{len(bad)} packed-fp32 instruction(s) with unsafe op_sel routing in the {len(texts)} device code object(s) of {lib}")
     return 1 if bad else 0
 
 

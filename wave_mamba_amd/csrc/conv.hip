@@ -1,0 +1,315 @@
+// conv.hip - C ABI over the dense convolutions (first-generation and wave-specialised kernels) and the patchify convolution.
+#include "host_common.h"
+#include "conv2d.hip.h"
+#include "conv2d_ws.hip.h"
+#include "patchify.hip.h"
+
+using namespace wm;
+
+template <int KS, int RW, int MT, bool G1X1 = false, bool F16 = false, bool LNIN = false>
+static int conv2d_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
+    constexpr int PAD = KS / 2;
+    constexpr int smem = ((4 * RW + 2 * PAD) * (wm::kCvTW + 2 * PAD) * 4 + (KS * KS + (G1X1 ? 1 : 0)) * MT * 2 * 64) * 16;   // input planes + weights
+    static bool configured[64] = {};
+    if (smem > 65536) {
+        const int rc = wm::lds_optin((const void*)wm::conv2d_mfma_kernel<KS, RW, MT, G1X1, F16, LNIN>, smem, configured);
+        if (rc) return rc;
+    }
+    const int ntiles = ((a.W + wm::kCvTW - 1) / wm::kCvTW) * ((a.H + 4 * RW - 1) / (4 * RW));
+    const dim3 grid((unsigned)(((ntiles + 7) / 8) * 8), (unsigned)B);
+    hipLaunchKernelGGL((wm::conv2d_mfma_kernel<KS, RW, MT, G1X1, F16, LNIN>), grid, dim3(256), smem, st, a);
+    return launch_status();
+}
+
+// Which 3x3 kernel: the persistent wave-specialised one (conv2d_ws.hip.h, one workgroup per compute unit) where it
+// pays - enough 64 x 8 tiles that every compute unit pipelines a few (UHD levels 1 and 2 and full resolution; at level 3
+// a workgroup gets one or two tiles and the first-generation kernel is 20-30 % faster), at most one epilogue operand and
+// then a single 32-channel row tile (two launches re-reading the input lose to the first-generation kernel's one) - and
+// where its 32-bit offsets hold.  wm_conv2d_select() pins the choice (parity tests run both on the same inputs: the
+// accumulation order per output element is the same, so the results are bit-identical).
+// rows per consumer wave (tile = 64 x 2 RW pixels) of the wave-specialised launches: two row tiles, one row tile, gated
+#ifndef WM_CONV_WS_RW2
+#define WM_CONV_WS_RW2 4
+#endif
+#ifndef WM_CONV_WS_RW1
+#define WM_CONV_WS_RW1 4
+#endif
+#ifndef WM_CONV_WS_RWG
+#define WM_CONV_WS_RWG 2
+#endif
+#ifndef WM_CONV_WS_NPW1
+#define WM_CONV_WS_NPW1 4              // producer waves of the one-row-tile launches
+#endif
+static std::atomic<int> g_conv_select{0};
+static int conv_select_mode() { return g_conv_select.load(std::memory_order_relaxed); }
+// th: tile rows of the launch that would run (2 x row tiles per workgroup)
+static bool conv_ws_enabled(const wm::Conv2dArgs& a, int B, int th) {
+    const int mode = conv_select_mode();
+    if (mode == 1) return false;
+    // 32-bit byte offsets inside one batch element of every tensor; gather indices in two registers
+    const long long cmax = std::max(std::max(a.Ca, a.xb ? a.Cbsrc : 0), a.Cout);
+    if (cmax * a.H * a.W * 4 >= (1ll << 32) || (a.xb_idx && a.Cb > 128)) return false;
+    if (a.gate && a.res) return false;
+    if (mode == 2) return true;
+    if ((a.gate || a.res) && a.mtot > 1) return false;
+    const long long ntiles = (long long)B * ((a.W + wm::kWsTW - 1) / wm::kWsTW) * ((a.H + th - 1) / th);
+    return ntiles >= 768;
+}
+
+template <int RW, int MT, bool G1X1 = false, bool EPI = false, int NPW = 4, bool F16 = false>
+static int conv2d_ws_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
+    using Cfg = wm::ConvWsCfg<RW, MT, G1X1, NPW>;
+    static bool configured[64] = {};
+    static int ncu[64] = {};
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return WM_EHIP;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!configured[dev]) {
+            if (hipFuncSetAttribute((const void*)wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    Cfg::LDS_BYTES) != hipSuccess) return WM_EHIP;
+            if (hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return WM_EHIP;
+            configured[dev] = true;
+        }
+    }
+    const long long ntiles = (long long)B * ((a.W + wm::kWsTW - 1) / wm::kWsTW) * ((a.H + Cfg::TH - 1) / Cfg::TH);
+    if (ntiles >= (1ll << 31)) return WM_EUNSUPPORTED;
+    const int cus = std::max(8, ncu[dev] & ~7);
+    const int G = (int)std::min<long long>(cus, ((ntiles + 7) / 8) * 8);
+    hipLaunchKernelGGL((wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16>), dim3((unsigned)G), dim3(256 + 64 * NPW), Cfg::LDS_BYTES, st, a, B);
+    return launch_status();
+}
+
+extern "C" {
+
+// nn.Sequential(nn.PixelUnshuffle(r), nn.Conv2d(r r Cin, Cout, 1)) of the UNet's image inputs (reference :1014-1025, :1043-1045) in one
+// kernel: an r x r / stride r convolution read straight from the image (patchify.hip.h).
+int wm_patchify_conv_fwd(const float* img, const float* weight, const float* bias, float* y, int B, int Cin, int Cout, int H, int W,
+                         int r, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (r != 2 && r != 4 && r != 8) return WM_EUNSUPPORTED;
+    if (H % r || W % r) return WM_EINVAL;
+    if (Cout != 16 && Cout != 32 && Cout != 48 && Cout != 64) return WM_EUNSUPPORTED;
+    const size_t lds = (size_t)Cin * r * r * Cout * sizeof(float);
+    if (lds > 64 * 1024) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!img || !weight || !y) return WM_ENULL;
+    if (!aligned16(img)) return WM_EALIGN;
+    if ((long long)B * Cin * H * W >= (1ll << 40)) return WM_EUNSUPPORTED;
+    const int Ho = H / r, Wo = W / r;
+    const int spr = (Wo + 255) / 256;
+    const long long nsegs = (long long)B * Ho * spr;
+    const int spb = (int)((nsegs + 4095) / 4096);
+    const long long blocks = (nsegs + spb - 1) / spb;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(18, st);
+#define WM_PF(R, CO) hipLaunchKernelGGL((patchify_conv_kernel<R, CO>), dim3((unsigned)blocks), dim3(256), lds, st, img, weight, bias, y, \
+                                        B, Cin, H, W, spr, nsegs, spb)
+#define WM_PFR(R) do { if (Cout == 16) WM_PF(R, 16); else if (Cout == 32) WM_PF(R, 32); else if (Cout == 48) WM_PF(R, 48); else WM_PF(R, 64); } while (0)
+    if (r == 2) WM_PFR(2); else if (r == 4) WM_PFR(4); else WM_PFR(8);
+#undef WM_PFR
+#undef WM_PF
+    return launch_status();
+}
+
+size_t wm_conv2d_wfrag_bytes(int Cout, int Cin, int ks) {
+    if (Cout <= 0 || Cin <= 0 || (ks != 1 && ks != 3)) return 0;
+    return (size_t)((Cin + 15) / 16) * ks * ks * ((Cout + 31) / 32) * 2 * 64 * 16;
+}
+
+int wm_conv2d_prep(const float* weight, void* wfrag, int Cout, int Cin, int ks, void* stream) {
+    if (Cout <= 0 || Cin <= 0) return WM_EINVAL;
+    if (ks != 1 && ks != 3) return WM_EUNSUPPORTED;
+    if (!weight || !wfrag) return WM_ENULL;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    const int nch = (Cin + 15) / 16, mtot = (Cout + 31) / 32;
+    const long long total = (long long)nch * ks * ks * mtot * 128;
+    hipLaunchKernelGGL(conv2d_prep_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       weight, (uint4*)wfrag, Cout, Cin, ks * ks, nch, mtot, (const float*)nullptr);
+    return launch_status();
+}
+
+int wm_conv2d_fwd(const float* xa, const float* xb, const int* xb_index, const void* wfrag, const float* bias,
+                  const float* gate, const float* residual, float* y, int B, int Ca, int Cb, int Cb_src, int Cout,
+                  int H, int W, int ks, void* stream) {
+    if (B < 0 || Ca <= 0 || Cb < 0 || Cout <= 0 || H < 0 || W < 0 || Cb_src < 0) return WM_EINVAL;
+    if (ks != 1 && ks != 3) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!xa || !wfrag || !y || (Cb > 0 && !xb)) return WM_ENULL;
+    if (Cb > 0 && Ca % 8 != 0) return WM_EUNSUPPORTED;   // an 8-channel fragment never straddles the two sources
+    if (Cb > 0 && !xb_index && Cb_src != Cb) return WM_EINVAL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = xa; a.xb = Cb > 0 ? xb : nullptr; a.xb_idx = Cb > 0 ? xb_index : nullptr; a.wfrag = (const uint4*)wfrag;
+    a.bias = bias; a.gate = gate; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
+    a.Ca = Ca; a.Cb = Cb; a.Cbsrc = Cb_src; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = (Ca + Cb + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    ProfScope ps(ks == 3 ? 13 : 14, st);
+    for (int mb = 0; mb < a.mtot;) {
+        a.mbase = mb;
+        const int left = a.mtot - mb;
+        int rc;
+        if (ks == 3) {
+#ifndef WM_CONV_RW1
+#define WM_CONV_RW1 3
+#endif
+            // 32 output channels: 12-row tiles (49 KB of LDS: three workgroups per compute unit, staging slots 93 % used)
+            // beat 16-row tiles (two workgroups, 80 %) by 4-13 %; 64 channels keep 16 rows (two accumulator sets)
+            if (conv_ws_enabled(a, B, 8)) {
+                if (gate || residual) { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, true>(a, B, st); mb += 1; }
+                else if (left >= 2) { rc = conv2d_ws_launch<WM_CONV_WS_RW2, 2>(a, B, st); mb += 2; }
+                else { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1>(a, B, st); mb += 1; }
+            } else if (left >= 2) { rc = conv2d_launch<3, 4, 2>(a, B, st); mb += 2; }
+            else { rc = conv2d_launch<3, WM_CONV_RW1, 1>(a, B, st); mb += 1; }
+        } else {
+            // 1x1 is bandwidth-bound: never read the input twice (3 row tiles in one launch on an 8-row tile)
+            if (left >= 3) { rc = conv2d_launch<1, 2, 3>(a, B, st); mb += 3; }
+            else if (left == 2) { rc = conv2d_launch<1, 4, 2>(a, B, st); mb += 2; }
+            else { rc = conv2d_launch<1, 4, 1>(a, B, st); mb += 1; }
+        }
+        if (rc) return rc;
+    }
+    return WM_OK;
+}
+
+// y = conv1x1(LayerNorm2d(x)) + bias (+ residual): the LayerNorm of a 32-channel map inside the 1x1 kernel's staging (conv2d.hip.h, LNIN).
+int wm_conv2d_ln_fwd(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* wfrag, const float* bias,
+                     const float* residual, float* y, int B, int Cin, int Cout, int H, int W, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (Cin != 32) return WM_EUNSUPPORTED;                 // callers run wm_layernorm2d_fwd + wm_conv2d_fwd
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !ln_weight || !ln_bias || !wfrag || !y) return WM_ENULL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = x; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
+    a.bias = bias; a.gate = nullptr; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
+    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = 2; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = ln_weight; a.ln_b = ln_bias; a.ln_eps = ln_eps;
+    ProfScope ps(14, st);
+    for (int mb = 0; mb < a.mtot;) {
+        a.mbase = mb;
+        const int left = a.mtot - mb;
+        int rc;
+        if (left >= 3) { rc = conv2d_launch<1, 2, 3, false, false, true>(a, B, st); mb += 3; }
+        else if (left == 2) { rc = conv2d_launch<1, 4, 2, false, false, true>(a, B, st); mb += 2; }
+        else { rc = conv2d_launch<1, 4, 1, false, false, true>(a, B, st); mb += 1; }
+        if (rc) return rc;
+    }
+    return WM_OK;
+}
+
+// The training form (conv2d.hip.h, fp16 split with per-tensor power-of-two scales): y = conv(x, w) + bias, ks in {1, 3}; wfrag from
+// cv_amax_prep_kernel with the SAME amax buffer {max |x|, max |w|} (device floats).
+static int conv2d_fwd_f16(const float* x, const void* wfrag, const float* amax, const float* bias, float* y, int B, int Cin, int Cout,
+                          int H, int W, int ks, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (ks != 1 && ks != 3) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !wfrag || !y || !amax) return WM_ENULL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = x; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
+    a.bias = bias; a.gate = nullptr; a.res = nullptr; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
+    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = (Cin + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = amax; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    ProfScope ps(ks == 3 ? 13 : 14, st);
+    for (int mb = 0; mb < a.mtot;) {
+        a.mbase = mb;
+        const int left = a.mtot - mb;
+        int rc;
+        if (ks == 3) {
+            if (conv_ws_enabled(a, B, 8)) {
+                if (left >= 2) { rc = conv2d_ws_launch<WM_CONV_WS_RW2, 2, false, false, 4, true>(a, B, st); mb += 2; }
+                else { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1, true>(a, B, st); mb += 1; }
+            } else if (left >= 2) { rc = conv2d_launch<3, 4, 2, false, true>(a, B, st); mb += 2; }
+            else { rc = conv2d_launch<3, WM_CONV_RW1, 1, false, true>(a, B, st); mb += 1; }
+        } else {
+            if (left >= 3) { rc = conv2d_launch<1, 2, 3, false, true>(a, B, st); mb += 3; }
+            else if (left == 2) { rc = conv2d_launch<1, 4, 2, false, true>(a, B, st); mb += 2; }
+            else { rc = conv2d_launch<1, 4, 1, false, true>(a, B, st); mb += 1; }
+        }
+        if (rc) return rc;
+    }
+    return WM_OK;
+}
+
+// The training step's convolution (fp16 split): `amax` (two floats; a slot of the caller's zeroed arena skips the memset node) and the
+// fragments in separate buffers, magnitudes + weight preparation in ONE launch (cv_amax_prep_kernel), then the convolution; dgrad: the
+// input-gradient convolution of the forward weight `weight` (conv2d.hip.h: cv_prep_item).  Two launches per convolution where round 4 had
+// four (memset, magnitudes, preparation, convolution) - and six with autograd's flipped copy of the weight.
+int wm_conv2d_f16_steps(const float* x, const float* weight, const float* bias, float* y, float* amax, void* wfrag, int B, int Cin,
+                        int Cout, int H, int W, int ks, int dgrad, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (ks != 1 && ks != 3) return WM_EUNSUPPORTED;
+    if (wm_conv2d_wfrag_bytes(Cout, Cin, ks) == 0) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !weight || !y || !amax || !wfrag) return WM_ENULL;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    if (zero_out(amax, 2 * sizeof(float), st) != hipSuccess) return WM_EHIP;
+    const long long nx = (long long)B * Cin * H * W, nw = (long long)Cout * Cin * ks * ks;
+    long long blocks = (nx / 4 + 256 * 8 - 1) / (256 * 8);           // >= 8 float4 per thread
+    blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
+    const int nch = (Cin + 15) / 16, mtot = (Cout + 31) / 32;
+    const long long items = (long long)nch * ks * ks * mtot * 128;
+    const int nprep = (int)(items <= 512 ? 1 : (items >= 32 * 512 ? 32 : (items + 511) / 512));   // ~2 fragment items per thread
+    hipLaunchKernelGGL(cv_amax_prep_kernel, dim3((unsigned)blocks + nprep), dim3(256), 0, st, x, nx, weight, nw, (unsigned*)amax,
+                       (uint4*)wfrag, Cout, Cin, ks * ks, nch, mtot, dgrad ? 1 : 0, nprep);
+    int rc = launch_status();
+    if (rc) return rc;
+    return conv2d_fwd_f16(x, wfrag, amax, bias, y, B, Cin, Cout, H, W, ks, stream);
+}
+
+int wm_conv2d_gated_fwd(const float* xa, const float* xb, const int* xb_index, const void* wfrag3, const void* wfrag1,
+                        const float* bias1, float* y, int B, int Ca, int Cb, int Cb_src, int Cout, int H, int W,
+                        void* stream) {
+    if (B < 0 || Ca <= 0 || Cb < 0 || Cout <= 0 || H < 0 || W < 0 || Cb_src < 0) return WM_EINVAL;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!xa || !wfrag3 || !wfrag1 || !y || (Cb > 0 && !xb)) return WM_ENULL;
+    if (Cb > 0 && Ca % 8 != 0) return WM_EUNSUPPORTED;
+    if (Cb > 0 && !xb_index && Cb_src != Cb) return WM_EINVAL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag3) || !aligned16(wfrag1)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = xa; a.xb = Cb > 0 ? xb : nullptr; a.xb_idx = Cb > 0 ? xb_index : nullptr; a.wfrag = (const uint4*)wfrag3;
+    a.bias = nullptr; a.gate = nullptr; a.res = nullptr; a.y = y; a.wfrag1 = (const uint4*)wfrag1; a.bias1 = bias1;
+    a.Ca = Ca; a.Cb = Cb; a.Cbsrc = Cb_src; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = (Ca + Cb + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    ProfScope ps(13, st);
+    for (int mb = 0; mb < a.mtot;) {
+        // two accumulator sets per wave: 64 channels x 8-row tiles read the input once (0.79 ms against 0.90 ms for
+        // two 32-channel x 16-row launches at UHD level 1, 64 -> 64); a last odd row tile takes the 16-row form
+        a.mbase = mb;
+        int rc;
+        const bool two = a.mtot - mb >= 2;                   // an odd tail runs one 32-channel tile on 8-row tiles
+        if (conv_ws_enabled(a, B, two ? 2 * WM_CONV_WS_RWG : 8)) {
+            if (two) { rc = conv2d_ws_launch<WM_CONV_WS_RWG, 2, true>(a, B, st); mb += 2; }
+            else { rc = conv2d_ws_launch<4, 1, true>(a, B, st); mb += 1; }
+        } else if (a.mtot - mb >= 2) { rc = conv2d_launch<3, 2, 2, true>(a, B, st); mb += 2; }
+        else { rc = conv2d_launch<3, 4, 1, true>(a, B, st); mb += 1; }
+        if (rc) return rc;
+    }
+    return WM_OK;
+}
+
+int wm_conv2d_select(int mode) {
+    if (mode < 0 || mode > 2) return WM_EINVAL;
+    g_conv_select.store(mode, std::memory_order_relaxed);
+    return WM_OK;
+}
+
+#if WM_CV_STAMP
+int wm_debug_conv_stamps(unsigned long long* out) {      // host buffer of 2 * 128 * 8 values
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(wm::g_cv_stamps), sizeof(unsigned long long) * 2 * 128 * 8);
+}
+#endif
+
+}  // extern "C"

@@ -1,0 +1,253 @@
+// haar_image.hip - C ABI over the Haar transforms, uint8 image I/O, the L1 loss and the image-quality metrics.
+#include "host_common.h"
+#include "haar.hip.h"
+#include "imageio.hip.h"
+#include "loss.hip.h"
+#include "metrics.hip.h"
+
+namespace wm {
+
+// ------------------------------------------------------------------------------------------------
+// Haar launchers
+// ------------------------------------------------------------------------------------------------
+template <typename Tf, typename Ts, bool ROUND>
+static int launch_analysis(const void* full, void* s0, void* s1, void* s2, void* s3, const HaarGeom& g,
+                           bool vec, hipStream_t st) {
+    const dim3 block(64, 4);
+    const int cols = vec ? (g.w + 3) / 4 : g.w;
+    const dim3 grid((unsigned)((g.rows + 3) / 4), (unsigned)((cols + 63) / 64));
+    if (vec)
+        hipLaunchKernelGGL((haar_analysis_kernel<Tf, Ts, ROUND, true>), grid, block, 0, st,
+                           (const Tf*)full, (Ts*)s0, (Ts*)s1, (Ts*)s2, (Ts*)s3, g);
+    else
+        hipLaunchKernelGGL((haar_analysis_kernel<Tf, Ts, ROUND, false>), grid, block, 0, st,
+                           (const Tf*)full, (Ts*)s0, (Ts*)s1, (Ts*)s2, (Ts*)s3, g);
+    return launch_status();
+}
+template <typename Ts, typename Tf, bool ROUND>
+static int launch_synthesis(const void* s0, const void* s1, const void* s2, const void* s3, void* full,
+                            const HaarGeom& g, bool vec, hipStream_t st) {
+    const dim3 block(64, 4);
+    const int cols = vec ? (g.w + 3) / 4 : g.w;
+    const dim3 grid((unsigned)((g.rows + 3) / 4), (unsigned)((cols + 63) / 64));
+    if (vec)
+        hipLaunchKernelGGL((haar_synthesis_kernel<Ts, Tf, ROUND, true>), grid, block, 0, st,
+                           (const Ts*)s0, (const Ts*)s1, (const Ts*)s2, (const Ts*)s3, (Tf*)full, g);
+    else
+        hipLaunchKernelGGL((haar_synthesis_kernel<Ts, Tf, ROUND, false>), grid, block, 0, st,
+                           (const Ts*)s0, (const Ts*)s1, (const Ts*)s2, (const Ts*)s3, (Tf*)full, g);
+    return launch_status();
+}
+
+static int haar_geom(HaarGeom& g, int B, int C, int h, int w, int64_t b0, int64_t b1, int64_t b2,
+                     int64_t b3) {
+    if (B < 0 || C < 0 || h < 0 || w < 0) return WM_EINVAL;
+    g.C = C; g.h = h; g.w = w; g.rows = (long long)B * C * h;
+    g.bs[0] = b0; g.bs[1] = b1; g.bs[2] = b2; g.bs[3] = b3;
+    if ((g.rows + 3) / 4 > 0x7fffffffLL) return WM_EINVAL;
+    return WM_OK;
+}
+// vector path: 4 sub-band columns per thread, every row start / stride 16-byte aligned on the
+// full-res side and 16 B (fp32) / 8 B (bf16) aligned on the sub-band side
+static bool haar_vec_ok(const HaarGeom& g, const void* full, const void* const s[4]) {
+    if (g.w % 4 != 0) return false;
+    if (!aligned16(full)) return false;
+    for (int k = 0; k < 4; ++k)
+        if (!aligned16(s[k]) || (g.bs[k] % 4) != 0) return false;
+    return true;
+}
+
+}  // namespace wm
+
+using namespace wm;
+
+// ================================================================================================
+// Image-quality metrics (csrc/metrics.hip.h): Y-channel PSNR / SSIM of uint8 image pairs, and the Y plane alone
+// ================================================================================================
+static bool met_image(MetImage& im, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int bgr) {
+    if (sn < 0 || sh < 0 || sw < 0 || sc < 0) return false;
+    im = MetImage{(long long)sn, (long long)sh, (long long)sw, (long long)sc, bgr ? 0 : 2, bgr ? 2 : 0};
+    return true;
+}
+
+static bool met_window(int N, int H, int W, int crop, int& Hc, int& Wc) {
+    if (N < 1 || H < 1 || W < 1 || crop < 0 || N > 65535) return false;
+    Hc = H - 2 * crop;
+    Wc = W - 2 * crop;
+    return Hc >= 1 && Wc >= 1;                         // crop >= min(H, W) / 2 leaves nothing to measure
+}
+
+extern "C" {
+
+int wm_dwt2d_fwd(const void* x, void* ll, void* hl, void* lh, void* hh, int B, int C, int H, int W,
+                 int dtype, void* stream) {
+    if (H % 2 != 0 || W % 2 != 0) return WM_EINVAL;        // reference: RuntimeError on odd sizes
+    HaarGeom g;
+    const int64_t bs = (int64_t)C * (H / 2) * (W / 2);
+    int rc = haar_geom(g, B, C, H / 2, W / 2, bs, bs, bs, bs);
+    if (rc) return rc;
+    if (g.rows == 0 || g.w == 0) return WM_OK;
+    if (!x || !ll || !hl || !lh || !hh) return WM_ENULL;
+    const void* s[4] = {ll, hl, lh, hh};
+    const bool vec = haar_vec_ok(g, x, s);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(0, st);
+    if (dtype == WM_F32) return launch_analysis<float, float, false>(x, ll, hl, lh, hh, g, vec, st);
+    if (dtype == WM_BF16) return launch_analysis<bf16_t, bf16_t, true>(x, ll, hl, lh, hh, g, vec, st);
+    return WM_EUNSUPPORTED;
+}
+
+int wm_dwt2d_bwd(const void* dll, const void* dhl, const void* dlh, const void* dhh, void* dx, int B,
+                 int C, int H, int W, int dtype, void* stream) {
+    if (H % 2 != 0 || W % 2 != 0) return WM_EINVAL;
+    HaarGeom g;
+    const int64_t bs = (int64_t)C * (H / 2) * (W / 2);
+    int rc = haar_geom(g, B, C, H / 2, W / 2, bs, bs, bs, bs);
+    if (rc) return rc;
+    if (g.rows == 0 || g.w == 0) return WM_OK;
+    if (!dx || !dll || !dhl || !dlh || !dhh) return WM_ENULL;
+    const void* s[4] = {dll, dhl, dlh, dhh};
+    const bool vec = haar_vec_ok(g, dx, s);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(1, st);
+    // the 2x2 Haar matrix (with the 1/2 scaling) is orthogonal: d(analysis) = synthesis
+    if (dtype == WM_F32) return launch_synthesis<float, float, false>(dll, dhl, dlh, dhh, dx, g, vec, st);
+    if (dtype == WM_BF16) return launch_synthesis<bf16_t, bf16_t, false>(dll, dhl, dlh, dhh, dx, g, vec, st);
+    return WM_EUNSUPPORTED;
+}
+
+int wm_idwt2d_fwd(const void* x1, const void* x2, const void* x3, const void* x4, int64_t bs1,
+                  int64_t bs2, int64_t bs3, int64_t bs4, float* out, int B, int C, int h, int w,
+                  int dtype, void* stream) {
+    HaarGeom g;
+    int rc = haar_geom(g, B, C, h, w, bs1, bs2, bs3, bs4);
+    if (rc) return rc;
+    if (g.rows == 0 || g.w == 0) return WM_OK;
+    if (!x1 || !x2 || !x3 || !x4 || !out) return WM_ENULL;
+    const void* s[4] = {x1, x2, x3, x4};
+    const bool vec = haar_vec_ok(g, out, s);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(1, st);
+    if (dtype == WM_F32) return launch_synthesis<float, float, false>(x1, x2, x3, x4, out, g, vec, st);
+    if (dtype == WM_BF16) return launch_synthesis<bf16_t, float, true>(x1, x2, x3, x4, out, g, vec, st);
+    return WM_EUNSUPPORTED;
+}
+
+int wm_idwt2d_bwd(const float* dout, void* d1, void* d2, void* d3, void* d4, int64_t bs1, int64_t bs2,
+                  int64_t bs3, int64_t bs4, int B, int C, int h, int w, int dtype, void* stream) {
+    HaarGeom g;
+    int rc = haar_geom(g, B, C, h, w, bs1, bs2, bs3, bs4);
+    if (rc) return rc;
+    if (g.rows == 0 || g.w == 0) return WM_OK;
+    if (!dout || !d1 || !d2 || !d3 || !d4) return WM_ENULL;
+    const void* s[4] = {d1, d2, d3, d4};
+    const bool vec = haar_vec_ok(g, dout, s);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(0, st);
+    if (dtype == WM_F32) return launch_analysis<float, float, false>(dout, d1, d2, d3, d4, g, vec, st);
+    if (dtype == WM_BF16) return launch_analysis<float, bf16_t, false>(dout, d1, d2, d3, d4, g, vec, st);
+    return WM_EUNSUPPORTED;
+}
+
+int wm_image_pre_u8(const uint8_t* image, float* out, int h, int w, int Hp, int Wp, int swap_rb, void* stream) {
+    if (h < 0 || w < 0 || Hp < h || Wp < w) return WM_EINVAL;
+    if (Hp == 0 || Wp == 0) return WM_OK;
+    if (h == 0 || w == 0) return WM_EINVAL;
+    if (Hp - h > h - 1 || Wp - w > w - 1) return WM_EINVAL;            // reflect padding needs pad < size
+    if (!image || !out) return WM_ENULL;
+    if (Hp > 65535) return WM_EUNSUPPORTED;
+    hipLaunchKernelGGL(image_pre_kernel, dim3((unsigned)((Wp + 255) / 256), (unsigned)Hp), dim3(256), 0, (hipStream_t)stream,
+                       image, out, h, w, Hp, Wp, swap_rb);
+    return launch_status();
+}
+
+int wm_image_post_u8(const float* in, uint8_t* image, int h, int w, int Hp, int Wp, int swap_rb, void* stream) {
+    if (h < 0 || w < 0 || Hp < h || Wp < w) return WM_EINVAL;
+    if (h == 0 || w == 0) return WM_OK;
+    if (!in || !image) return WM_ENULL;
+    if (h > 65535) return WM_EUNSUPPORTED;
+    hipLaunchKernelGGL(image_post_kernel, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, (hipStream_t)stream,
+                       in, image, h, w, Hp, Wp, swap_rb);
+    return launch_status();
+}
+
+// mean |a - b| over n elements -> out[0] (zeroed here, by a kernel); ga = gout[0] * sign(a - b) / n
+int wm_l1_mean_fwd(const float* a, const float* b, float* out, int64_t n, void* stream) {
+    if (n < 0) return WM_EINVAL;
+    if (!out) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = zero_out(out, sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return WM_OK;                                     // (torch returns nan for an empty mean; callers never ask)
+    if (!a || !b) return WM_ENULL;
+    const int vec = (n % 4 == 0) && aligned16(a) && aligned16(b) ? 1 : 0;
+    long long blocks = ((vec ? n / 4 : n) + 256 * 8 - 1) / (256 * 8);
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(l1_mean_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, out, (long long)n, 1.0f / (float)n, vec);
+    return launch_status();
+}
+int wm_l1_mean_bwd(const float* a, const float* b, const float* gout, float* ga, int64_t n, void* stream) {
+    if (n < 0) return WM_EINVAL;
+    if (n == 0) return WM_OK;
+    if (!a || !b || !gout || !ga) return WM_ENULL;
+    const int vec = (n % 4 == 0) && aligned16(a) && aligned16(b) && aligned16(ga) ? 1 : 0;
+    long long blocks = ((vec ? n / 4 : n) + 256 * 4 - 1) / (256 * 4);
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(l1_mean_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, gout, ga, (long long)n,
+                       1.0f / (float)n, vec);
+    return launch_status();
+}
+
+
+size_t wm_psnr_ssim_y_workspace_bytes(int N, int H, int W, int crop) {
+    int Hc, Wc;
+    if (!met_window(N, H, W, crop, Hc, Wc)) return 0;
+    const size_t tiles = (size_t)((Wc + MET_TW - 1) / MET_TW) * (size_t)((Hc + MET_TH - 1) / MET_TH);
+    return (size_t)N * tiles * 2 * sizeof(double);
+}
+
+int wm_psnr_ssim_y_u8(const uint8_t* a, const uint8_t* b, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W,
+                      int crop, int bgr, double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    int Hc, Wc;
+    MetImage im;
+    if (!met_window(N, H, W, crop, Hc, Wc) || !met_image(im, sn, sh, sw, sc, bgr)) return WM_EINVAL;
+    if (!a || !b || !out || !workspace) return WM_ENULL;
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 7u) return WM_EALIGN;
+    if (workspace_bytes < wm_psnr_ssim_y_workspace_bytes(N, H, W, crop)) return WM_EWORKSPACE;
+    MetGauss gw;                                           // cv2.getGaussianKernel(11, 1.5): exp(-(i - 5)^2 / (2 1.5^2)), normalised
+    double sum = 0.0;
+    for (int i = 0; i < MET_TAPS; ++i) {
+        const double x = i - (MET_TAPS - 1) * 0.5;
+        gw.g[i] = exp(-0.5 / (1.5 * 1.5) * x * x);
+        sum += gw.g[i];
+    }
+    for (int i = 0; i < MET_TAPS; ++i) gw.g[i] *= 1.0 / sum;
+    const int tx = (Wc + MET_TW - 1) / MET_TW, ty = (Hc + MET_TH - 1) / MET_TH;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(psnr_ssim_tile_kernel, dim3((unsigned)tx, (unsigned)ty, (unsigned)N), dim3(256), 0, st, a, b, im, crop, Hc, Wc,
+                       gw, part);
+    int rc = launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(psnr_ssim_finish_kernel, dim3((unsigned)N), dim3(256), 0, st, (const double*)part, tx * ty, (double)Hc * Wc,
+                       out);
+    return launch_status();
+}
+
+int wm_y_channel_u8(const uint8_t* img, int64_t sn, int64_t sh, int64_t sw, int64_t sc, int N, int H, int W, int bgr, float* y,
+                    void* stream) {
+    int Hc, Wc;
+    MetImage im;
+    if (!met_window(N, H, W, 0, Hc, Wc) || !met_image(im, sn, sh, sw, sc, bgr)) return WM_EINVAL;
+    if (!img || !y) return WM_ENULL;
+    if (reinterpret_cast<uintptr_t>(y) & 3u) return WM_EALIGN;
+    const long long total = (long long)N * H * W;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(y_channel_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, img, im, H, W, total, y);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -1,0 +1,79 @@
+// host_common.h - what the library's translation units (csrc/*.hip) share on the host side.  No kernels here: a kernel is
+// defined (or instantiated) in exactly one unit.  Process-wide state is DEFINED in common.hip and declared here; everything
+// that crosses units has hidden visibility, so the library's dynamic symbols stay the wm_* entry points and the kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <array>
+#include <atomic>
+#include <list>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "../../include/wavemamba_hip.h"
+
+#define WM_HIDDEN __attribute__((visibility("hidden")))
+
+namespace wm {
+
+// ------------------------------------------------------------------------------------------------
+// profiling hooks: HIP events on the launch stream around each kernel class
+// ------------------------------------------------------------------------------------------------
+struct Prof {
+    std::mutex mu;
+    unsigned mask = 0;                                          // bit k: record kernel class k
+    std::vector<hipEvent_t> pool;                               // recycled events
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> rec[WM_PROF_NKERNELS];
+    hipEvent_t get() {
+        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
+        hipEvent_t e; hipEventCreate(&e); return e;
+    }
+};
+WM_HIDDEN extern Prof g_prof;                                   // one per process (common.hip): wm_prof_collect sees every unit's launches
+
+struct ProfScope {
+    int id; hipStream_t s; hipEvent_t e0 = nullptr, e1 = nullptr; bool active;
+    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_), active((g_prof.mask >> id_) & 1u) {
+        if (!active) return;
+        std::lock_guard<std::mutex> lk(g_prof.mu);
+        e0 = g_prof.get(); e1 = g_prof.get();
+        hipEventRecord(e0, s);
+    }
+    ~ProfScope() {
+        if (!active) return;
+        hipEventRecord(e1, s);
+        std::lock_guard<std::mutex> lk(g_prof.mu);
+        g_prof.rec[id].emplace_back(e0, e1);
+    }
+};
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline int launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WM_OK : (int)e;
+}
+
+// Zeroing by a kernel (zero_fill_kernel, common.hip), never hipMemsetAsync.  bytes % 4 == 0 and a 4-byte aligned pointer.
+WM_HIDDEN hipError_t zero_async(void* p, size_t bytes, hipStream_t st);
+// zero_async unless the buffer lies inside a registered zero arena (wm_zero_arena_register, one registry per process)
+WM_HIDDEN hipError_t zero_out(void* p, size_t bytes, hipStream_t st);
+// two small gradient buffers: one launch when the caller allocated them back to back
+WM_HIDDEN hipError_t zero_pair(float* a, size_t na, float* b, size_t nb, hipStream_t st);
+
+// > 64 KB of dynamic LDS is an opt-in per kernel function AND per device: one flag per (instantiation, device).
+// `flags` is the caller's function-local static array; returns WM_OK or WM_EHIP.
+WM_HIDDEN int lds_optin(const void* fn, int bytes, bool (&flags)[64]);
+
+}  // namespace wm
+
+// Plane-dtype dispatch: runs CALL once with TP = float (plane_dtype == WM_F32) or TP = bf16_t (otherwise; callers have checked
+// plane_dtype beforehand).  bf16_t comes with the kernel headers of the units that use this.
+#define WM_PLANE_DISPATCH(plane_dtype, CALL)                          \
+    do {                                                              \
+        if ((plane_dtype) == WM_F32) { using TP = float; CALL; }      \
+        else { using TP = bf16_t; CALL; }                             \
+    } while (0)

@@ -1,0 +1,395 @@
+// lfss.hip - C ABI over the LFSS glue: depth-wise 3x3, the fused block kernels, LayerNorm, gates and scaled adds.
+#include "host_common.h"
+#include "dwconv.hip.h"
+#include "lfss.hip.h"
+#include "lfss_mfma.hip.h"
+#include "gates.hip.h"
+
+using namespace wm;
+
+// lanes per strip row of the depth-wise kernels (dwconv.hip.h): narrow maps put 2 / 4 planes side by side in a wave
+static int dw_lanes_per_row(int W, bool vec) { return !vec || W > 128 ? 64 : (W > 64 ? 32 : 16); }
+// rows per strip: 16 (every input row fetched 18 / 16 times), or 8 / 4 on small problems - a strip is a chain of dependent row
+// fetches, and 16-row strips of a 64 x 64 map are 128-384 workgroups for 256 compute units (21 us per weight-gradient launch at
+// BASELINE config 3's level 3, whatever the lanes did)
+static int dw_strip_rows(int H, long long column_blocks, long long plane_groups) {
+    const long long waves16 = column_blocks * ((H + kDwRows - 1) / kDwRows) * plane_groups;
+    return waves16 >= 2048 ? kDwRows : (waves16 >= 1024 ? 8 : 4);
+}
+
+// Launch geometry of the C = 32 matrix-core kernels (lfss_mfma.hip.h): groups of 64 positions, `gpw` of them per wave, enough
+// waves to fill `target_waves` slots, four waves per workgroup.
+struct Lfss32Grid { int ngl, gpw; long long ngroups; dim3 grid; };
+static Lfss32Grid lfss32_grid(int B, long long L, int target_waves) {
+    Lfss32Grid g;
+    g.ngl = (int)((L + 63) / 64);
+    g.ngroups = (long long)B * g.ngl;
+    g.gpw = lfss_groups_per_wave(g.ngroups, target_waves);
+    const long long waves = (g.ngroups + g.gpw - 1) / g.gpw;
+    g.grid = dim3((unsigned)((waves + 3) / 4));
+    return g;
+}
+
+// The C = 32 middle kernel (lfss_mid_mfma_kernel): RZ = false reads the gate plane z, RZ = true recomputes it from `tok` (ln_1 +
+// in_proj rows [D, 2D)) and takes no z.
+template <bool RZ>
+static int lfss_mid32_launch(const void* ysum, int ny, int64_t ystride, const void* z, const float* tok, int tok_nchw, const float* ln1_w,
+                             const float* ln1_b, float ln1_eps, const float* in_proj_weight, const float* out_norm_w,
+                             const float* out_norm_b, float out_norm_eps, const float* out_proj_weight, const float* skip_scale,
+                             const float* ln2_w, const float* ln2_b, float ln2_eps, const float* conv1_weight,
+                             const float* conv1_bias, float* tok1, void* f, int B, int64_t L, int plane_dtype, hipStream_t st) {
+    const Lfss32Grid g = lfss32_grid(B, L, 1024 * (RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES));
+    ProfScope ps(9, st);
+#define WM_MID(NY) WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((lfss_mid_mfma_kernel<NY, TP, RZ>), g.grid, dim3(256), 0, st, \
+                           (const TP*)ysum, (long long)ystride, (const TP*)z, tok, tok_nchw, out_norm_w, out_norm_b, out_norm_eps,    \
+                           out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias, tok1, (TP*)f, B,             \
+                           (long long)L, g.ngl, g.ngroups, g.gpw, ln1_w, ln1_b, ln1_eps, in_proj_weight))
+    if (ny == 4) WM_MID(4); else WM_MID(1);
+#undef WM_MID
+    return launch_status();
+}
+
+extern "C" {
+
+int wm_dwconv3x3_fwd(const void* x, const float* weight, const float* bias, void* y, int B, int C,
+                     int H, int W, int act, int plane_dtype, void* stream) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return WM_EINVAL;
+    const int flip = (act >> 2) & 1;                  // act + 4: the taps rotated by 180 degrees (the input gradient's convolution)
+    act &= 3;
+    if (act < 0 || act > 2 || (plane_dtype != WM_F32 && plane_dtype != WM_BF16)) return WM_EUNSUPPORTED;
+    const long long planes = (long long)B * C;
+    if (planes == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !weight || !y) return WM_ENULL;
+    const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(y);      // (bf16: 8-byte accesses, covered by the same test)
+    const int lpr = dw_lanes_per_row(W, vec);
+    const long long pgroups = (planes + 64 / lpr - 1) / (64 / lpr);
+    const dim3 block(64, 4);
+    const int rows = dw_strip_rows(H, (W + 4 * lpr - 1) / (4 * lpr), pgroups);
+    const dim3 grid((unsigned)((W + 4 * lpr - 1) / (4 * lpr)), (unsigned)((H + 4 * rows - 1) / (4 * rows)),
+                    (unsigned)(pgroups < 65535 ? pgroups : 65535));
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(act == 1 ? 7 : 17, st);       // + SiLU: SS2D's conv2d (:486-487, hot path); the others belong to the HFE branch / the ffn
+#define WM_DW1(ACT, VEC, LPR)                                                                                                 \
+    WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((dwconv3x3_kernel<ACT, VEC, TP, LPR>), grid, block, 0, st, (const TP*)x,   \
+                                                      weight, bias, (TP*)y, C, H, W, planes, rows, flip))
+#define WM_DW(ACT)                                                                                                            \
+    do {                                                                                                                      \
+        if (!vec) WM_DW1(ACT, false, 64); else if (lpr == 64) WM_DW1(ACT, true, 64);                                          \
+        else if (lpr == 32) WM_DW1(ACT, true, 32); else WM_DW1(ACT, true, 16);                                                \
+    } while (0)
+    if (act == 1) WM_DW(1); else if (act == 2) WM_DW(2); else WM_DW(0);
+#undef WM_DW
+#undef WM_DW1
+    return launch_status();
+}
+
+#define WM_LFSS_DISPATCH(PROFCLASS, KERNEL, ...)                                                   \
+    do {                                                                                           \
+        const long long total = (long long)B * L;                                                  \
+        if (total == 0) return WM_OK;                                                              \
+        const dim3 grid((unsigned)((total + 255) / 256)), block(256);                              \
+        hipStream_t st = (hipStream_t)stream;                                                      \
+        ProfScope ps(PROFCLASS, st);                                                               \
+        if (C == 32) hipLaunchKernelGGL((KERNEL<32>), grid, block, 0, st, __VA_ARGS__);            \
+        else if (C == 16) hipLaunchKernelGGL((KERNEL<16>), grid, block, 0, st, __VA_ARGS__);       \
+        else if (C == 8) hipLaunchKernelGGL((KERNEL<8>), grid, block, 0, st, __VA_ARGS__);         \
+        else return WM_EUNSUPPORTED;                                                               \
+        return launch_status();                                                                    \
+    } while (0)
+
+int wm_lfss_in_fwd(const float* tok, int tok_nchw, const float* ln_w, const float* ln_b, float ln_eps,
+                   const float* in_proj_weight, void* x_, void* z_, int B, int64_t L, int C, int plane_dtype, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32)) return WM_EUNSUPPORTED;    // bf16 planes: C = 32 kernels
+    float* x = (float*)x_; float* z = (float*)z_;
+    // z == NULL (C == 32 only): the gate half is not written - the block's wm_lfss_mid_rz_fwd recomputes it
+    if (B && L && (!tok || !ln_w || !ln_b || !in_proj_weight || !x || (!z && C != 32))) return WM_ENULL;
+    if (!tok_nchw && !aligned16(tok)) return WM_EALIGN;
+    if (C == 32 && B && L) {
+        const Lfss32Grid g = lfss32_grid(B, L, 1024 * WM_LFSS_IN_WAVES);
+        hipStream_t st = (hipStream_t)stream;
+        ProfScope ps(5, st);
+        WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL(lfss_in_mfma_kernel<TP>, g.grid, dim3(256), 0, st, tok, tok_nchw, ln_w, ln_b,
+                                                          ln_eps, in_proj_weight, (TP*)x_, (TP*)z_, B, (long long)L, g.ngl, g.ngroups, g.gpw));
+        return launch_status();
+    }
+    WM_LFSS_DISPATCH(5, lfss_in_kernel, tok, tok_nchw, ln_w, ln_b, ln_eps, in_proj_weight, x, z, B, (long long)L);
+}
+
+int wm_lfss_mid_fwd(const void* ysum_, int ny, int64_t ystride, const void* z_, const float* tok, int tok_nchw, const float* out_norm_w,
+                    const float* out_norm_b, float out_norm_eps, const float* out_proj_weight,
+                    const float* skip_scale, const float* ln2_w, const float* ln2_b, float ln2_eps,
+                    const float* conv1_weight, const float* conv1_bias, float* tok1, void* f_, int B, int64_t L,
+                    int C, int plane_dtype, void* stream) {
+    if (B < 0 || L < 0 || (ny != 1 && ny != 4)) return WM_EINVAL;
+    if (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32)) return WM_EUNSUPPORTED;
+    const float* ysum = (const float*)ysum_; const float* z = (const float*)z_; float* f = (float*)f_;
+    if (B && L && (!ysum || !z || !tok || !out_norm_w || !out_norm_b || !out_proj_weight || !skip_scale || !ln2_w ||
+                   !ln2_b || !conv1_weight || !conv1_bias || !tok1 || !f)) return WM_ENULL;
+    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    if (C == 32 && B && L)                                   // the shipped width: projections on the matrix cores
+        return lfss_mid32_launch<false>(ysum_, ny, ystride, z_, tok, tok_nchw, nullptr, nullptr, 0.0f, nullptr, out_norm_w, out_norm_b,
+                                        out_norm_eps, out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
+                                        tok1, f_, B, L, plane_dtype, (hipStream_t)stream);
+    WM_LFSS_DISPATCH(9, lfss_mid_kernel, ysum, ny, (long long)ystride, z, tok, tok_nchw, out_norm_w, out_norm_b, out_norm_eps, out_proj_weight,
+                     skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias, tok1, f, B, (long long)L);
+}
+
+// wm_lfss_mid_fwd with the gate z RECOMPUTED from `tok` (ln_1 + in_proj rows [D, 2D) on the matrix cores, bit-identical to
+// wm_lfss_in_fwd's z in fp32 planes) instead of read: C == 32 only (WM_EUNSUPPORTED otherwise: callers keep z and wm_lfss_mid_fwd).
+int wm_lfss_mid_rz_fwd(const void* ysum_, int ny, int64_t ystride, const float* tok, int tok_nchw, const float* ln1_w,
+                       const float* ln1_b, float ln1_eps, const float* in_proj_weight, const float* out_norm_w,
+                       const float* out_norm_b, float out_norm_eps, const float* out_proj_weight,
+                       const float* skip_scale, const float* ln2_w, const float* ln2_b, float ln2_eps,
+                       const float* conv1_weight, const float* conv1_bias, float* tok1, void* f_, int B, int64_t L,
+                       int C, int plane_dtype, void* stream) {
+    if (B < 0 || L < 0 || (ny != 1 && ny != 4)) return WM_EINVAL;
+    if (C != 32 || (plane_dtype != WM_F32 && plane_dtype != WM_BF16)) return WM_EUNSUPPORTED;
+    if (B == 0 || L == 0) return WM_OK;
+    if (!ysum_ || !tok || !ln1_w || !ln1_b || !in_proj_weight || !out_norm_w || !out_norm_b || !out_proj_weight || !skip_scale ||
+        !ln2_w || !ln2_b || !conv1_weight || !conv1_bias || !tok1 || !f_) return WM_ENULL;
+    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    return lfss_mid32_launch<true>(ysum_, ny, ystride, nullptr, tok, tok_nchw, ln1_w, ln1_b, ln1_eps, in_proj_weight, out_norm_w,
+                                   out_norm_b, out_norm_eps, out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight,
+                                   conv1_bias, tok1, f_, B, L, plane_dtype, (hipStream_t)stream);
+}
+
+int wm_lfss_out_fwd(const void* fc_, const float* tok1, const float* conv3_weight, const float* conv3_bias,
+                    const float* skip_scale2, float* out, int out_nchw, int B, int64_t L, int C, int plane_dtype, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32)) return WM_EUNSUPPORTED;
+    const float* fc = (const float*)fc_;
+    if (B && L && (!fc || !tok1 || !conv3_weight || !conv3_bias || !skip_scale2 || !out)) return WM_ENULL;
+    if (!aligned16(tok1) || (!out_nchw && !aligned16(out))) return WM_EALIGN;
+    if (C == 32 && B && L) {
+        const Lfss32Grid g = lfss32_grid(B, L, 2048);
+        hipStream_t st = (hipStream_t)stream;
+        ProfScope ps(11, st);
+        WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL(lfss_out_mfma_kernel<TP>, g.grid, dim3(256), 0, st, (const TP*)fc_, tok1, conv3_weight,
+                                                          conv3_bias, skip_scale2, out, out_nchw, B, (long long)L, g.ngl, g.ngroups, g.gpw));
+        return launch_status();
+    }
+    WM_LFSS_DISPATCH(11, lfss_out_kernel, fc, tok1, conv3_weight, conv3_bias, skip_scale2, out, out_nchw, B, (long long)L);
+}
+
+int wm_lfss_out_conv_fwd(const void* f_, const float* conv2_weight, const float* conv2_bias, const float* tok1,
+                         const float* conv3_weight, const float* conv3_bias, const float* skip_scale2, float* out,
+                         int out_nchw, int B, int H, int W, int C, int plane_dtype, void* stream) {
+    if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (C != 32 || W % 32 != 0) return WM_EUNSUPPORTED;          // callers fall back to wm_dwconv3x3_fwd + wm_lfss_out_fwd
+    if (plane_dtype != WM_F32 && plane_dtype != WM_BF16) return WM_EUNSUPPORTED;
+    const long long L = (long long)H * W;
+    if (B == 0 || L == 0) return WM_OK;
+    if (L > 0x1fffffffLL) return WM_EUNSUPPORTED;                // 32-bit byte offsets inside one channel plane
+    if (!f_ || !conv2_weight || !tok1 || !conv3_weight || !conv3_bias || !skip_scale2 || !out) return WM_ENULL;
+    if (!aligned16(tok1) || (!out_nchw && !aligned16(out))) return WM_EALIGN;
+    // accumulating row-window form (round 6, lfss_out_conv_acc_kernel<4>: four output rows of a 64-column strip per wave pass, the
+    // closing product accumulated in registers over groups of eight gated channels, one coalesced load per tap row + lane shifts):
+    // W % 64 == 0 and >= 2^18 positions.  Measured (profiles/r06/lfss_out_conv_forms.txt, ms per call at UHD levels 1 / 2): banded
+    // one-row form 0.464 / 0.087 (round 4), row windows in LDS R = 2 0.405 / 0.088 (round 4-5; deleted), this form R = 2 0.401 /
+    // 0.084, R = 4 0.346 / 0.069; its double-buffered variant 0.338-0.351 / 0.074 (not kept).  Bit-identical outputs in all forms.
+    if (W % 64 == 0 && (long long)B * L >= (1ll << 18)) {
+        constexpr int R = 4;
+        const int nstrips = W / 64, nbands = (H + R - 1) / R;
+        // bands per walk (a wave walks consecutive bands of its strip): enough walks for two rounds of the 2,048 resident waves
+        int bpw = (int)(((long long)B * nbands * nstrips + 4095) / 4096);
+        if (bpw < 1) bpw = 1;
+        if (bpw > 8) bpw = 8;
+        const int nchunks = (nbands + bpw - 1) / bpw;
+        const long long nwalks = (long long)B * nchunks * nstrips;
+        hipStream_t st3 = (hipStream_t)stream;
+        ProfScope ps3(11, st3);
+        WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((lfss_out_conv_acc_kernel<R, TP>), dim3((unsigned)((nwalks + 3) / 4)), dim3(256), 0,
+                                                          st3, (const TP*)f_, conv2_weight, conv2_bias, tok1, conv3_weight, conv3_bias,
+                                                          skip_scale2, out, out_nchw, B, H, W, nstrips, nbands, bpw, nchunks, nwalks));
+        return launch_status();
+    }
+    // groups per image row for the kernel's banded (column-major) group order (0: linear order, maps whose width is not a multiple of 64)
+    const int gpr = (W % 64 == 0) ? W / 64 : 0;
+    const Lfss32Grid g = lfss32_grid(B, L, 2048);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(11, st);
+    WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL(lfss_out_conv_mfma_kernel<TP>, g.grid, dim3(256), 0, st, (const TP*)f_, conv2_weight,
+                                                      conv2_bias, tok1, conv3_weight, conv3_bias, skip_scale2, out, out_nchw, B, H, W,
+                                                      g.ngl, g.ngroups, g.gpw, gpr));
+    return launch_status();
+}
+
+int wm_layernorm2d_fwd(const float* x, const float* weight, const float* bias, float eps, float* y, int B,
+                       int64_t L, int C, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (B && L && (!x || !weight || !bias || !y)) return WM_ENULL;
+    if (C == 64) {                                       // SS2D.out_norm on (B, D, L) planes (NCHW training path)
+        const long long total = (long long)B * L;
+        if (total == 0) return WM_OK;
+        hipStream_t st = (hipStream_t)stream;
+        ProfScope ps(16, st);
+        hipLaunchKernelGGL((layernorm2d_kernel<64>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, weight, bias,
+                           eps, y, B, (long long)L);
+        return launch_status();
+    }
+    WM_LFSS_DISPATCH(16, layernorm2d_kernel, x, weight, bias, eps, y, B, (long long)L);
+}
+
+int wm_dwconv3x3_wgrad(const float* x, const float* gy, float* dW, float* db, int B, int C, int H, int W,
+                       void* stream) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (C == 0) return WM_OK;
+    if (!dW) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = zero_pair(dW, (size_t)C * 9, db, (size_t)C, st);
+    if (e != hipSuccess) return (int)e;
+    const long long planes = (long long)B * C;
+    if (planes == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !gy) return WM_ENULL;
+    const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(gy);
+    const int lpr = dw_lanes_per_row(W, vec);
+    const long long pgroups = (planes + 64 / lpr - 1) / (64 / lpr);
+    const dim3 block(64, 4);
+    const int rows = kDwRows;                  // (shorter strips on small maps: more atomics - twice the time at config 3's level 3)
+    const dim3 grid((unsigned)((W + 4 * lpr - 1) / (4 * lpr)), (unsigned)((H + 4 * rows - 1) / (4 * rows)),
+                    (unsigned)(pgroups < 65535 ? pgroups : 65535));
+    if (!vec) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<false, 64>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
+    else if (lpr == 64) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 64>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
+    else if (lpr == 32) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 32>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
+    else hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 16>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
+    return launch_status();
+}
+
+int wm_layernorm2d_bwd(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight,
+                       float* dbias, int B, int64_t L, int C, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (C != 8 && C != 16 && C != 32 && C != 64) return WM_EUNSUPPORTED;
+    if (!dweight || !dbias) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = zero_pair(dweight, (size_t)C, dbias, (size_t)C, st);
+    if (e != hipSuccess) return (int)e;
+    const long long total = (long long)B * L;
+    if (total == 0) return WM_OK;
+    if (!x || !weight || !gy || !gx) return WM_ENULL;
+    const int tpp = C >= 32 ? 2 : 1;                     // threads per pixel (layernorm2d_bwd_pair_kernel)
+    long long blocks = (total * tpp + 255) / 256;
+    if (blocks > 512) blocks = 512;                      // grid-stride: few blocks -> few atomics per channel
+    const dim3 grid((unsigned)blocks), block(256);
+    if (C == 64) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<64>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    else if (C == 32) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<32>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    else if (C == 16) hipLaunchKernelGGL((layernorm2d_bwd_kernel<16>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    else hipLaunchKernelGGL((layernorm2d_bwd_kernel<8>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    return launch_status();
+}
+
+int wm_layernorm_tok_fwd(const float* x, const float* weight, const float* bias, float eps, float* y, int64_t T, int C,
+                         void* stream) {
+    if (T < 0) return WM_EINVAL;
+    if (C != 8 && C != 16 && C != 32 && C != 64) return WM_EUNSUPPORTED;
+    if (T == 0) return WM_OK;
+    if (!x || !weight || !bias || !y) return WM_ENULL;
+    if (!aligned16(x) || !aligned16(y) || !aligned16(weight) || !aligned16(bias)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int tpb = 256 / (C / 4);
+    long long blocks = (T + tpb - 1) / tpb;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    const dim3 grid((unsigned)blocks), block(256);
+#define WM_LNT(CC) hipLaunchKernelGGL((layernorm_tok_kernel<CC>), grid, block, 0, st, (const float4*)x, (const float4*)weight, \
+                                      (const float4*)bias, eps, (float4*)y, (long long)T)
+    if (C == 64) WM_LNT(64); else if (C == 32) WM_LNT(32); else if (C == 16) WM_LNT(16); else WM_LNT(8);
+#undef WM_LNT
+    return launch_status();
+}
+
+int wm_layernorm_tok_bwd(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight,
+                         float* dbias, int64_t T, int C, void* stream) {
+    if (T < 0) return WM_EINVAL;
+    if (C != 8 && C != 16 && C != 32 && C != 64) return WM_EUNSUPPORTED;
+    if (!dweight || !dbias) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = zero_pair(dweight, (size_t)C, dbias, (size_t)C, st);
+    if (e != hipSuccess) return (int)e;
+    if (T == 0) return WM_OK;
+    if (!x || !weight || !gy || !gx) return WM_ENULL;
+    if (!aligned16(x) || !aligned16(gy) || !aligned16(gx) || !aligned16(weight)) return WM_EALIGN;
+    const int tpb = 256 / (C / 4);
+    long long blocks = (T + tpb - 1) / tpb;
+    if (blocks > 1024) blocks = 1024;                    // grid-stride: few blocks -> few atomics per channel
+    const dim3 grid((unsigned)blocks), block(256);
+#define WM_LNTB(CC) hipLaunchKernelGGL((layernorm_tok_bwd_kernel<CC>), grid, block, 0, st, (const float4*)x, (const float4*)weight, \
+                                       (const float4*)gy, eps, (float4*)gx, dweight, dbias, (long long)T)
+    if (C == 64) WM_LNTB(64); else if (C == 32) WM_LNTB(32); else if (C == 16) WM_LNTB(16); else WM_LNTB(8);
+#undef WM_LNTB
+    return launch_status();
+}
+
+// act: 1 = SiLU, 2 = GELU (erf).  a / b / out (and g / ga / gb) are (B, per_b) with batch strides in elements.
+int wm_gate_fwd(const float* a, const float* b, float* out, int act, int B, int64_t per_b, int64_t stride_a, int64_t stride_b,
+                int64_t stride_out, void* stream) {
+    if (B < 0 || per_b < 0) return WM_EINVAL;
+    if (act < 1 || act > 3) return WM_EUNSUPPORTED;
+    if (B == 0 || per_b == 0) return WM_OK;
+    if (!a || !b || !out) return WM_ENULL;
+    if (B > 65535) return WM_EUNSUPPORTED;
+    GateArgs p{a, b, nullptr, out, nullptr, nullptr, per_b, stride_a, stride_b, 0, stride_out, 0, 0};
+    const bool vec = per_b % 4 == 0 && stride_a % 4 == 0 && stride_b % 4 == 0 && stride_out % 4 == 0 && aligned16(a) &&
+                     aligned16(b) && aligned16(out);
+    const dim3 grid((unsigned)((per_b + 1023) / 1024), (unsigned)B), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define WM_GATE(ACT) do { if (vec) hipLaunchKernelGGL((gate_kernel<ACT, false, true>), grid, block, 0, st, p);          \
+                          else hipLaunchKernelGGL((gate_kernel<ACT, false, false>), grid, block, 0, st, p); } while (0)
+    if (act == 1) WM_GATE(1); else if (act == 2) WM_GATE(2); else WM_GATE(3);
+#undef WM_GATE
+    return launch_status();
+}
+
+int wm_gate_bwd(const float* a, const float* b, const float* g, float* ga, float* gb, int act, int B, int64_t per_b,
+                int64_t stride_a, int64_t stride_b, int64_t stride_g, int64_t stride_ga, int64_t stride_gb, void* stream) {
+    if (B < 0 || per_b < 0) return WM_EINVAL;
+    if (act < 1 || act > 3) return WM_EUNSUPPORTED;
+    if (B == 0 || per_b == 0) return WM_OK;
+    if (!a || !b || !g || !ga || !gb) return WM_ENULL;
+    if (B > 65535) return WM_EUNSUPPORTED;
+    GateArgs p{a, b, g, nullptr, ga, gb, per_b, stride_a, stride_b, stride_g, 0, stride_ga, stride_gb};
+    const bool vec = per_b % 4 == 0 && stride_a % 4 == 0 && stride_b % 4 == 0 && stride_g % 4 == 0 && stride_ga % 4 == 0 &&
+                     stride_gb % 4 == 0 && aligned16(a) && aligned16(b) && aligned16(g) && aligned16(ga) && aligned16(gb);
+    const dim3 grid((unsigned)((per_b + 1023) / 1024), (unsigned)B), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define WM_GATE(ACT) do { if (vec) hipLaunchKernelGGL((gate_kernel<ACT, true, true>), grid, block, 0, st, p);           \
+                          else hipLaunchKernelGGL((gate_kernel<ACT, true, false>), grid, block, 0, st, p); } while (0)
+    if (act == 1) WM_GATE(1); else if (act == 2) WM_GATE(2); else WM_GATE(3);
+#undef WM_GATE
+    return launch_status();
+}
+
+int wm_scale_add_fwd(const float* x, const float* scale, const float* o, float* out, int B, int C, int64_t L, void* stream) {
+    if (B < 0 || C < 0 || L < 0) return WM_EINVAL;
+    if (B == 0 || C == 0 || L == 0) return WM_OK;
+    if (!x || !scale || !o || !out) return WM_ENULL;
+    if ((long long)B * C > 65535) return WM_EUNSUPPORTED;
+    const bool vec = L % 4 == 0 && aligned16(x) && aligned16(o) && aligned16(out);
+    const dim3 grid((unsigned)((L + 1023) / 1024), (unsigned)(B * C)), block(256);
+    if (vec) hipLaunchKernelGGL(scale_add_fwd_kernel<true>, grid, block, 0, (hipStream_t)stream, x, scale, o, out, C, (long long)L);
+    else hipLaunchKernelGGL(scale_add_fwd_kernel<false>, grid, block, 0, (hipStream_t)stream, x, scale, o, out, C, (long long)L);
+    return launch_status();
+}
+
+int wm_scale_add_bwd(const float* g, const float* x, const float* scale, float* gx, float* gscale, int B, int C, int64_t L,
+                     void* stream) {
+    if (B < 0 || C < 0 || L < 0) return WM_EINVAL;
+    if (C == 0) return WM_OK;
+    if (!gscale) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = zero_out(gscale, (size_t)C * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    if (B == 0 || L == 0) return WM_OK;
+    if (!g || !x || !scale || !gx) return WM_ENULL;
+    if ((long long)B * C > 65535) return WM_EUNSUPPORTED;
+    const bool vec = L % 4 == 0 && aligned16(g) && aligned16(x) && aligned16(gx);
+    long long bpp = (L + 1023) / 1024;                       // blocks per plane: <= 8 (scale_add_bwd_kernel), >= ~2048 in all if the map allows
+    const long long want = (2048 + (long long)B * C - 1) / ((long long)B * C);
+    const long long cap = want > 8 ? want : 8;
+    if (bpp > cap) bpp = cap;
+    const dim3 grid((unsigned)bpp, (unsigned)(B * C)), block(256);
+    if (vec) hipLaunchKernelGGL(scale_add_bwd_kernel<true>, grid, block, 0, st, g, x, scale, gx, gscale, C, (long long)L);
+    else hipLaunchKernelGGL(scale_add_bwd_kernel<false>, grid, block, 0, st, g, x, scale, gx, gscale, C, (long long)L);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -374,7 +374,7 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
 def ss2d_core_supported(d_inner, d_state, dt_rank, width=None, height=None):
     """Shapes the fused HIP core covers (else: direction glue + selective_scan_fn).  Any map size (widths that are not
     a multiple of 4 take the kernels' element-wise tile accesses); with `width` and `height`, maps beyond the kernels'
-    32-bit element offsets (d_inner * H * W >= 2^31, wavemamba_hip.hip: core_plan) are refused here instead of at the
+    32-bit element offsets (d_inner * H * W >= 2^31, csrc/scan_fwd.hip: core_plan) are refused here instead of at the
     call."""
     if d_inner > 64 or dt_rank > 4 or d_state > 32:
         return False
