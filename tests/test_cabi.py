@@ -169,3 +169,76 @@ def test_zero_arena_registry_bookkeeping():
         assert lib.wm_zero_arena_unregister(base) == _lib.WM_OK
     assert lib.wm_zero_arena_unregister(base) == _lib.WM_EINVAL
     assert lib.wm_zero_arena_register(base, 64) == _lib.WM_OK and lib.wm_zero_arena_unregister(base) == _lib.WM_OK
+
+
+def declared_prototypes():
+    """include/wavemamba_hip.h -> {name: (return kind, [argument kinds])}, a kind being 'pointer' or the C scalar type."""
+    text = open(os.path.join(ROOT, "include", "wavemamba_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+
+    def kind(decl, named):
+        if "*" in decl or "[" in decl:
+            return "pointer"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named else words)
+
+    protos = {}
+    for ret, name, args in re.findall(r"^([A-Za-z_][\w \t\*]*?)\s*\b(wm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        args = [a.strip() for a in args.split(",")]
+        if args in ([""], ["void"]):
+            args = []
+        assert name not in protos, f"{name} is declared twice"
+        protos[name] = (kind(ret, False), [kind(a, True) for a in args])
+    return protos
+
+
+def ctypes_kind(t):
+    scalars = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float",
+               ctypes.c_uint: "unsigned", None: "void"}
+    if t in scalars:                                # (c_size_t is an alias of an integer type distinct from c_int / c_int64 here)
+        return scalars[t]
+    assert t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer), t
+    return "pointer"
+
+
+def test_binding_signatures_match_the_header_argument_by_argument():
+    """_lib.SIGNATURES against the prototypes of include/wavemamba_hip.h, position by position: the argument count, each argument's
+    kind (pointer, int, int64_t, size_t, float, unsigned) and the return kind.  A wrong type or count in the binding would shift
+    every later argument of a launch; the set of names alone (above) would not notice."""
+    assert len({ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_uint, ctypes.c_float}) == 5
+    protos = declared_prototypes()
+    assert set(protos) == set(declared_symbols()) == set(_lib.SIGNATURES)
+    assert len(protos) >= 63
+    for name, (ret, args) in protos.items():
+        res, argtypes = _lib.SIGNATURES[name]
+        assert all(k in ("pointer", "int", "int64_t", "size_t", "float", "unsigned") for k in args), (name, args)
+        assert ctypes_kind(res) == ret, f"{name}: the binding returns {ctypes_kind(res)}, the header {ret}"
+        assert len(argtypes) == len(args), f"{name}: the binding passes {len(argtypes)} arguments, the header takes {len(args)}"
+        for i, (t, k) in enumerate(zip(argtypes, args)):
+            assert ctypes_kind(t) == k, f"{name}: argument {i} is {ctypes_kind(t)} in the binding, {k} in the header"
+
+
+def test_launch_names_in_ops_are_bound_entry_points():
+    """wave_mamba_amd/ops.py names the entry point of every launch as a string (ops._launch looks it up and reports errors
+    under it): every such literal is a key of _lib.SIGNATURES whose last argument is the stream, and nothing launches otherwise."""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, "wave_mamba_amd", "ops.py")).read())
+    launched = []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id == "_launch":
+            name = node.args[1]
+            assert isinstance(name, ast.Constant) and isinstance(name.value, str), f"line {node.lineno}: the name must be a literal"
+            launched.append(name.value)
+        if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(r"wm_[a-z0-9_]+", node.value):
+            assert node.value in _lib.SIGNATURES, f"ops.py line {node.lineno}: {node.value!r} is not an entry point of the library"
+    assert len(launched) >= 45 and len(set(launched)) >= 43, sorted(set(launched))      # 45 launch sites of 43 entry points today
+    for name in launched:
+        assert name in _lib.SIGNATURES, f"{name!r} is launched but not bound"
+        assert _lib.SIGNATURES[name][0] is ctypes.c_int and _lib.SIGNATURES[name][1][-1] is ctypes.c_void_p, name
+    # no launch beside the helper: an entry point called as an attribute of the library takes no stream
+    text = re.sub(r'""".*?"""', "", open(os.path.join(ROOT, "wave_mamba_amd", "ops.py")).read(), flags=re.S)
+    direct = set(re.findall(r"\.(wm_[a-z0-9_]+)\b", text))
+    assert direct <= {"wm_zero_arena_register", "wm_zero_arena_unregister", "wm_event_synchronize_relaxed", "wm_conv2d_select",
+                      "wm_conv2d_wfrag_bytes", "wm_ss2d_core_prep_bytes", "wm_prof_enable", "wm_prof_collect"} | {
+                          n for n in _lib.SIGNATURES if n.endswith("_workspace_bytes")}, sorted(direct)

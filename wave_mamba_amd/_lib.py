@@ -16,7 +16,7 @@ ABI_VERSION = 32
 _c = ctypes
 _p, _i, _i64, _sz = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_size_t
 
-# name -> (restype, argtypes); mirrors include/wavemamba_hip.h one to one
+# name -> (restype, argtypes); mirrors include/wavemamba_hip.h one to one (tests/test_cabi.py: argument by argument)
 SIGNATURES = {
     "wm_abi_version": (_i, []),
     "wm_build_id": (_c.c_char_p, []),

@@ -13,6 +13,7 @@ gfx950).  PyTorch only supplies device memory, the current stream and autograd p
 NO CPU / eager fallback: a non-CUDA tensor or a missing library raises.
 """
 import os
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -42,8 +43,22 @@ def _dtype_code(t, name):
     raise RuntimeError(f"{name}: unsupported dtype {t.dtype} (float32 and bfloat16 are implemented)")
 
 
-def _ptr(t):
+def _ptr(t):                # (for tests and tools that call the library directly; the operators below go through _launch)
     return None if t is None else t.data_ptr()
+
+
+def _launch(dev, name, *args, status=False):
+    """The one way a kernel-launching entry point of the library is called: on device `dev`, on that device's current stream
+    (every launching entry point takes `void* stream` last), tensors passed as their data pointers (None and raw integer
+    addresses - sub-band and GLU-half offsets - go through as they are), a non-zero status raised under the entry point's
+    own name.  status=True: the status is returned instead, for a caller that tells a refusal from an error."""
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = _stream()
+        rc = getattr(lib, name)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], stream)
+    if status:
+        return rc
+    check(rc, name)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -69,7 +84,6 @@ def _zeros_small(n, device):
     stream.  Larger than 64 KB, or under graph capture: uninitialised memory (the library zeroes it itself)."""
     if n > 16384 or torch.cuda.is_current_stream_capturing():
         return torch.empty(n, dtype=torch.float32, device=device)
-    import weakref
     lib = _lib.load()
     key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
     step = (n + 63) & ~63                                  # 256-byte slots
@@ -127,7 +141,6 @@ def get_plane_dtype():
 class _DWT(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        lib = _lib.load()
         _require_cuda("dwt_init", x)
         if x.dim() != 4:
             raise RuntimeError(f"dwt_init: expected a 4-D NCHW tensor, got {tuple(x.shape)}")
@@ -138,22 +151,17 @@ class _DWT(torch.autograd.Function):
         code = _dtype_code(x, "dwt_init")
         x = x.contiguous()
         outs = [torch.empty((B, C, H // 2, W // 2), dtype=x.dtype, device=x.device) for _ in range(4)]
-        with torch.cuda.device(x.device):
-            check(lib.wm_dwt2d_fwd(_ptr(x), *[_ptr(o) for o in outs], B, C, H, W, code, _stream()),
-                  "wm_dwt2d_fwd")
+        _launch(x.device, "wm_dwt2d_fwd", x, *outs, B, C, H, W, code)
         ctx.shape = (B, C, H, W)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, g_ll, g_hl, g_lh, g_hh):
-        lib = _lib.load()
         B, C, H, W = ctx.shape
         gs = [g.contiguous() for g in (g_ll, g_hl, g_lh, g_hh)]
         code = _dtype_code(gs[0], "dwt_init.backward")
         dx = torch.empty((B, C, H, W), dtype=gs[0].dtype, device=gs[0].device)
-        with torch.cuda.device(dx.device):
-            check(lib.wm_dwt2d_bwd(*[_ptr(g) for g in gs], _ptr(dx), B, C, H, W, code, _stream()),
-                  "wm_dwt2d_bwd")
+        _launch(dx.device, "wm_dwt2d_bwd", *gs, dx, B, C, H, W, code)
         return dx
 
 
@@ -164,7 +172,6 @@ class _IWT(torch.autograd.Function):
     def forward(ctx, x_l, x_h):
         # x_h is None: x_l is the reference's concatenated (B, 4C, h, w) tensor.
         # else: x_l (B, C, h, w) and x_h (B, 3C, h, w) - upFRG's un-concatenated pair (:1006).
-        lib = _lib.load()
         _require_cuda("iwt_init", x_l, x_h)
         x_l = x_l.contiguous()
         if x_h is None:
@@ -190,14 +197,12 @@ class _IWT(torch.autograd.Function):
             strides = [C * hw] + [3 * C * hw] * 3
             code = _dtype_code(x_l, "iwt_init")
         out = torch.empty((B, C, 2 * h, 2 * w), dtype=torch.float32, device=x_l.device)  # always fp32
-        with torch.cuda.device(out.device):
-            check(lib.wm_idwt2d_fwd(*ptrs, *strides, _ptr(out), B, C, h, w, code, _stream()), "wm_idwt2d_fwd")
+        _launch(out.device, "wm_idwt2d_fwd", *ptrs, *strides, out, B, C, h, w, code)
         ctx.geom = (B, C, h, w, x_h is None, x_l.dtype)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         B, C, h, w, cat, dt = ctx.geom
         g = g.contiguous().float()
         hw = h * w
@@ -214,8 +219,7 @@ class _IWT(torch.autograd.Function):
             es = d_l.element_size()
             ptrs = [d_l.data_ptr()] + [d_h.data_ptr() + k * C * hw * es for k in range(3)]
             strides = [C * hw] + [3 * C * hw] * 3
-        with torch.cuda.device(g.device):
-            check(lib.wm_idwt2d_bwd(_ptr(g), *ptrs, *strides, B, C, h, w, code, _stream()), "wm_idwt2d_bwd")
+        _launch(g.device, "wm_idwt2d_bwd", g, *ptrs, *strides, B, C, h, w, code)
         return d_l, d_h
 
 
@@ -295,11 +299,8 @@ def _scan_forward(u, delta, A, B, C, D, z, delta_bias, delta_softplus, want_last
     last = torch.empty((batch, dim, N), dtype=torch.float32, device=u.device) if want_last else None
     ws_bytes = lib.wm_selscan_fwd_workspace_bytes(batch, dim, L, N, G)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device) if ws_bytes else None
-    with torch.cuda.device(u.device):
-        check(lib.wm_selscan_fwd(_ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D), _ptr(z),
-                                 _ptr(delta_bias), _ptr(out), _ptr(last), _ptr(ws), ws_bytes,
-                                 batch, dim, L, N, G, int(bool(delta_softplus)), _stream()),
-              "wm_selscan_fwd")
+    _launch(u.device, "wm_selscan_fwd", u, delta, A, B, C, D, z, delta_bias, out, last, ws, ws_bytes,
+            batch, dim, L, N, G, int(bool(delta_softplus)))
     return out, last
 
 
@@ -330,12 +331,8 @@ class _SelectiveScan(torch.autograd.Function):
         dbias = torch.empty_like(delta_bias) if delta_bias is not None else None
         ws_bytes = lib.wm_selscan_bwd_workspace_bytes(batch, dim, L, N, G)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device) if ws_bytes else None
-        with torch.cuda.device(u.device):
-            check(lib.wm_selscan_bwd(_ptr(u), _ptr(delta), _ptr(A), _ptr(B), _ptr(C), _ptr(D),
-                                     _ptr(delta_bias), _ptr(dout), _ptr(du), _ptr(ddelta), _ptr(dA),
-                                     _ptr(dB), _ptr(dC), _ptr(dD), _ptr(dbias), _ptr(ws), ws_bytes,
-                                     batch, dim, L, N, G, int(ctx.delta_softplus), _stream()),
-                  "wm_selscan_bwd")
+        _launch(u.device, "wm_selscan_bwd", u, delta, A, B, C, D, delta_bias, dout, du, ddelta, dA, dB, dC, dD, dbias,
+                ws, ws_bytes, batch, dim, L, N, G, int(ctx.delta_softplus))
         return du, ddelta, dA, dB, dC, dD, dbias, None, None
 
 
@@ -407,7 +404,55 @@ def _host_wait_under_capture(event):
     check(_lib.load().wm_event_synchronize_relaxed(event.cuda_event), "wm_event_synchronize_relaxed")
 
 
-_CORE_PREP_CACHE = {}   # id(x_proj_weight) -> (weakrefs, data_ptrs, versions, prepared buffer, done event, stream)
+class _PreparedCache:
+    """Prepared device copies of parameters (the SS2D core's constants, the convolutions' weight fragments), one per tuple of
+    parameter objects, keyed by the first of them.  An entry is valid while every object is the same one with the same
+    `data_ptr`, `_version` and dtype - a write through `.data` bumps no version: see conv2d_cache_clear - and leaves when its
+    first parameter dies.  It remembers the stream it was built on and an event recorded behind the preparation kernel, so a
+    use from another stream never reads the copy before it is complete nor sees it freed under a pending launch."""
+
+    def __init__(self):
+        self._ent = {}      # id(params[0]) -> (weakrefs, signature, buffer, done event, producer stream, eviction hook)
+
+    @staticmethod
+    def _sig(params):
+        return tuple((p.data_ptr(), p._version, p.dtype) for p in params)
+
+    def get(self, params):
+        """The valid cached copy for `params`, made safe to use on the current stream - or None."""
+        ent = self._ent.get(id(params[0]))
+        if ent is None or not all(r() is p for r, p in zip(ent[0], params)) or ent[1] != self._sig(params):
+            return None
+        buf, ev, stream = ent[2:5]
+        cur = torch.cuda.current_stream(params[0].device)
+        if stream != cur.cuda_stream:
+            if torch.cuda.is_current_stream_capturing():
+                # an event recorded outside the capture cannot be waited for inside it: block the HOST until the producer
+                # (a warm-up forward on another stream that was never joined) is done, then the buffer is simply there
+                _host_wait_under_capture(ev)
+            else:
+                cur.wait_event(ev)
+                buf.record_stream(cur)
+        return buf
+
+    def put(self, params, buf):
+        """`buf` was just prepared from `params` on the current stream: keep it."""
+        key = id(params[0])
+        cur = torch.cuda.current_stream(params[0].device)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        old = self._ent.get(key)        # an entry under this key is this object's (a dead object's entry is gone): one hook per object
+        hook = old[5] if old is not None else weakref.finalize(params[0], self._ent.pop, key, None)
+        self._ent[key] = ([weakref.ref(p) for p in params], self._sig(params), buf, ev, cur.cuda_stream, hook)
+
+    def clear(self):
+        for ent in self._ent.values():
+            ent[5].detach()
+        self._ent.clear()
+
+
+_CORE_PREP_CACHE = _PreparedCache()
+_WFRAG_CACHE = _PreparedCache()
 
 
 def _ss2d_core_prepared(params):
@@ -416,36 +461,16 @@ def _ss2d_core_prepared(params):
     parameters are unchanged (`_version`, storage) - inference runs the core 14 times per image with static parameters.
     Returns None (the call prepares for itself) for parameters that require grad (training updates them every step),
     under graph capture, and for temporaries."""
-    import weakref
     if any((not isinstance(p, torch.nn.Parameter)) or p.requires_grad and torch.is_grad_enabled() for p in params):
         return None
-    key = id(params[0])
-    cur = torch.cuda.current_stream(params[0].device)
-    sig = tuple((p.data_ptr(), p._version, p.dtype) for p in params)
-    ent = _CORE_PREP_CACHE.get(key)
-    if ent is not None and all(r() is p for r, p in zip(ent[0], params)) and ent[1] == sig:
-        if ent[4] != cur.cuda_stream:
-            if torch.cuda.is_current_stream_capturing():
-                # an event recorded outside the capture cannot be waited for inside it: block the HOST until the producer
-                # (a warm-up forward on another stream that was never joined) is done, then the buffer is simply there
-                _host_wait_under_capture(ent[3])
-            else:
-                cur.wait_event(ent[3])
-                ent[2].record_stream(cur)
-        return ent[2]
-    if torch.cuda.is_current_stream_capturing():
-        return None                                  # cold cache under capture: the call prepares for itself, inside the graph
-    lib = _lib.load()
-    f = [p.detach().contiguous().float() for p in params]
+    buf = _CORE_PREP_CACHE.get(params)
+    if buf is not None or torch.cuda.is_current_stream_capturing():
+        return buf                                   # cold cache under capture: None, the call prepares for itself inside the graph
+    f = [_w(p) for p in params]
     D, R, N = f[1].shape[1], f[1].shape[2], f[3].shape[1]
-    buf = torch.empty(lib.wm_ss2d_core_prep_bytes(N), dtype=torch.uint8, device=f[0].device)
-    with torch.cuda.device(f[0].device):
-        check(lib.wm_ss2d_core_prep(*[_ptr(t) for t in f], _ptr(buf), D, N, R, _stream()), "wm_ss2d_core_prep")
-    ev = torch.cuda.Event()
-    ev.record(cur)
-    if key not in _CORE_PREP_CACHE:                  # one finalizer per parameter object, not one per rebuild
-        weakref.finalize(params[0], _CORE_PREP_CACHE.pop, key, None)
-    _CORE_PREP_CACHE[key] = ([weakref.ref(p) for p in params], sig, buf, ev, cur.cuda_stream)
+    buf = torch.empty(_lib.load().wm_ss2d_core_prep_bytes(N), dtype=torch.uint8, device=f[0].device)
+    _launch(buf.device, "wm_ss2d_core_prep", *f, buf, D, N, R)
+    _CORE_PREP_CACHE.put(params, buf)
     return buf
 
 
@@ -465,11 +490,8 @@ def _ss2d_core_fwd(f, merged, prepared=None, separate=False):
         outs = list(torch.empty((4, B, D, L), dtype=x.dtype, device=x.device).unbind(0))
     ws_bytes = lib.wm_ss2d_core_fwd_workspace_bytes(B, D, H, W, N, R, int(merged))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    ptrs = [_ptr(o) for o in outs] + [None] * (4 - len(outs))
-    with torch.cuda.device(x.device):
-        check(lib.wm_ss2d_core_fwd(*[_ptr(t) for t in f], *ptrs, int(merged), _ptr(ws), ws_bytes,
-                                   None if prepared is None else _ptr(prepared),
-                                   B, D, H, W, N, R, _dtype_code(x, "ss2d_core"), _stream()), "wm_ss2d_core_fwd")
+    _launch(x.device, "wm_ss2d_core_fwd", *f, *outs, *[None] * (4 - len(outs)), int(merged), ws, ws_bytes, prepared,
+            B, D, H, W, N, R, _dtype_code(x, "ss2d_core"))
     return outs
 
 
@@ -501,9 +523,7 @@ class _SS2DCoreFn(torch.autograd.Function):
                 torch.empty_like(f[4]), torch.empty_like(f[5])]
         ws_bytes = lib.wm_ss2d_core_bwd_workspace_bytes(B, D, H, W, N, R)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib.wm_ss2d_core_bwd(*[_ptr(t) for t in f], *[_ptr(t) for t in dy], *[_ptr(t) for t in outs],
-                                       _ptr(ws), ws_bytes, B, D, H, W, N, R, _stream()), "wm_ss2d_core_bwd")
+        _launch(x.device, "wm_ss2d_core_bwd", *f, *dy, *outs, ws, ws_bytes, B, D, H, W, N, R)
         return (None, *outs)
 
 
@@ -512,7 +532,6 @@ def ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, merg
     x (B, D, H, W) fp32 -> (y_row_fwd, y_row_rev, y_col_fwd, y_col_rev), each (B, D, H*W) in
     row-major l - the reference's return order; merged=True returns their sum (what :490 computes).
     Differentiable w.r.t. x and the five parameters (HIP backward, wm_ss2d_core_bwd)."""
-    _lib.load()
     _require_cuda("ss2d_core", x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)
     _ss2d_core_shapes(x, x_proj_weight, dt_projs_weight, A_logs)
     args = (x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)
@@ -551,7 +570,6 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
     tok: (B, L, C) tokens, or (B, C, H, W) when tok_nchw.  `blk` supplies the parameters (an LFSSBlock
     module: ln_1, self_attention, skip_scale, conv_blk, ln_2, skip_scale2).  Returns (B, L, C) tokens or
     (B, C, H, W) when out_nchw."""
-    lib = _lib.load()
     _require_cuda("lfss_block_forward", tok)
     H, W = x_size
     L = H * W
@@ -560,54 +578,43 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
     B = tok.shape[0]
     tok = tok.contiguous().float()
     dev = tok.device
-    st = _stream()
     # bf16 planes: the C = 32 kernels on maps with 16-byte tile accesses (W % 4 == 0); else fp32 planes
     pd = _PLANE_DTYPE if (C == 32 and W % 4 == 0) else torch.float32
     code = WM_F32 if pd == torch.float32 else WM_BF16
     # C == 32: the gate z is recomputed by the block's middle kernel from the tokens it reads anyway (wm_lfss_mid_rz_fwd, bit-identical
     # in fp32 planes) - lfss_in writes the x half only (ops._RECOMPUTE_Z = False: the written / re-read z, tests and tools)
     rz = C == 32 and _RECOMPUTE_Z
+    # the ffn's depth-wise 3x3 inside the closing kernel: fc (conv2's output) never reaches HBM
+    fuse_out = C == 32 and W % 32 == 0 and _FUSE_OUT_CONV
+    # the parameters the block's own launches read, each normalised once per call (nothing is kept across calls: a write through
+    # `.data` shows in the next forward); the depth-wise convolutions outside the fused closing kernel normalise their own
+    ln1 = (_w(blk.ln_1.weight), _w(blk.ln_1.bias), float(blk.ln_1.eps), _w(ss.in_proj.weight))
+    core_params = (ss.x_proj_weight, ss.dt_projs_weight, ss.dt_projs_bias, ss.A_logs, ss.Ds)
+    core_w = [_w(t) for t in core_params]
+    mid = (_w(ss.out_norm.weight), _w(ss.out_norm.bias), float(ss.out_norm.eps), _w(ss.out_proj.weight), _w(blk.skip_scale),
+           _w(blk.ln_2.weight), _w(blk.ln_2.bias), float(blk.ln_2.eps), _w(ff.conv1.weight), _w(ff.conv1.bias))
+    conv2 = (_w(ff.conv2.weight), None if ff.conv2.bias is None else _w(ff.conv2.bias)) if fuse_out else None
+    tail = (_w(ff.conv3.weight), _w(ff.conv3.bias), _w(blk.skip_scale2))
+
     z = None if rz else torch.empty((B, D, L), dtype=pd, device=dev)
     x = torch.empty((B, D, H, W), dtype=pd, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.wm_lfss_in_fwd(_ptr(tok), int(tok_nchw), _ptr(_w(blk.ln_1.weight)), _ptr(_w(blk.ln_1.bias)),
-                                 float(blk.ln_1.eps), _ptr(_w(ss.in_proj.weight)), _ptr(x), _ptr(z), B, L, C, code, st),
-              "wm_lfss_in_fwd")
+    _launch(dev, "wm_lfss_in_fwd", tok, int(tok_nchw), *ln1, x, z, B, L, C, code)
     xc = dwconv3x3(x, ss.conv2d.weight, ss.conv2d.bias, "silu")
     # the four directions' outputs stay separate (one (4, B, D, L) allocation); lfss_mid adds them as it loads (:490)
-    core_params = (ss.x_proj_weight, ss.dt_projs_weight, ss.dt_projs_bias, ss.A_logs, ss.Ds)
     ny = 4
-    y4 = _ss2d_core_fwd([xc] + [_w(t) for t in core_params], merged=0, prepared=_ss2d_core_prepared(core_params))
+    y4 = _ss2d_core_fwd([xc] + core_w, merged=0, prepared=_ss2d_core_prepared(core_params))
     tok1 = torch.empty((B, L, C), dtype=torch.float32, device=dev)
     f = torch.empty((B, D, H, W), dtype=pd, device=dev)
-    with torch.cuda.device(dev):
-        if rz:
-            check(lib.wm_lfss_mid_rz_fwd(_ptr(y4[0]), ny, B * D * L, _ptr(tok), int(tok_nchw), _ptr(_w(blk.ln_1.weight)),
-                                         _ptr(_w(blk.ln_1.bias)), float(blk.ln_1.eps), _ptr(_w(ss.in_proj.weight)),
-                                         _ptr(_w(ss.out_norm.weight)), _ptr(_w(ss.out_norm.bias)), float(ss.out_norm.eps),
-                                         _ptr(_w(ss.out_proj.weight)), _ptr(_w(blk.skip_scale)), _ptr(_w(blk.ln_2.weight)),
-                                         _ptr(_w(blk.ln_2.bias)), float(blk.ln_2.eps), _ptr(_w(ff.conv1.weight)),
-                                         _ptr(_w(ff.conv1.bias)), _ptr(tok1), _ptr(f), B, L, C, code, st), "wm_lfss_mid_rz_fwd")
-        else:
-            check(lib.wm_lfss_mid_fwd(_ptr(y4[0]), ny, B * D * L, _ptr(z), _ptr(tok), int(tok_nchw), _ptr(_w(ss.out_norm.weight)),
-                                      _ptr(_w(ss.out_norm.bias)), float(ss.out_norm.eps), _ptr(_w(ss.out_proj.weight)),
-                                      _ptr(_w(blk.skip_scale)), _ptr(_w(blk.ln_2.weight)), _ptr(_w(blk.ln_2.bias)),
-                                      float(blk.ln_2.eps), _ptr(_w(ff.conv1.weight)), _ptr(_w(ff.conv1.bias)),
-                                      _ptr(tok1), _ptr(f), B, L, C, code, st), "wm_lfss_mid_fwd")
+    if rz:
+        _launch(dev, "wm_lfss_mid_rz_fwd", y4[0], ny, B * D * L, tok, int(tok_nchw), *ln1, *mid, tok1, f, B, L, C, code)
+    else:
+        _launch(dev, "wm_lfss_mid_fwd", y4[0], ny, B * D * L, z, tok, int(tok_nchw), *mid, tok1, f, B, L, C, code)
     out = torch.empty((B, C, H, W) if out_nchw else (B, L, C), dtype=torch.float32, device=dev)
-    if C == 32 and W % 32 == 0 and _FUSE_OUT_CONV:
-        # the ffn's depth-wise 3x3 inside the closing kernel: fc (conv2's output) never reaches HBM
-        with torch.cuda.device(dev):
-            check(lib.wm_lfss_out_conv_fwd(_ptr(f), _ptr(_w(ff.conv2.weight)),
-                                           None if ff.conv2.bias is None else _ptr(_w(ff.conv2.bias)), _ptr(tok1),
-                                           _ptr(_w(ff.conv3.weight)), _ptr(_w(ff.conv3.bias)), _ptr(_w(blk.skip_scale2)),
-                                           _ptr(out), int(out_nchw), B, H, W, C, code, st), "wm_lfss_out_conv_fwd")
+    if fuse_out:
+        _launch(dev, "wm_lfss_out_conv_fwd", f, *conv2, tok1, *tail, out, int(out_nchw), B, H, W, C, code)
         return out
     fc = dwconv3x3(f, ff.conv2.weight, ff.conv2.bias, "none")
-    with torch.cuda.device(dev):
-        check(lib.wm_lfss_out_fwd(_ptr(fc), _ptr(tok1), _ptr(_w(ff.conv3.weight)), _ptr(_w(ff.conv3.bias)),
-                                  _ptr(_w(blk.skip_scale2)), _ptr(out), int(out_nchw), B, L, C, code, st),
-              "wm_lfss_out_fwd")
+    _launch(dev, "wm_lfss_out_fwd", fc, tok1, *tail, out, int(out_nchw), B, L, C, code)
     return out
 
 
@@ -616,16 +623,13 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
 # ------------------------------------------------------------------------------------------------
 def layernorm2d(x, weight, bias, eps):
     """Per-pixel LayerNorm over channels of an NCHW fp32 map (reference LayerNorm2d, :532-569)."""
-    lib = _lib.load()
     _require_cuda("layernorm2d", x, weight, bias)
     B, C, H, W = x.shape
     if C not in (8, 16, 32, 64) or x.dtype != torch.float32:
         raise NotImplementedError("layernorm2d: fp32, C in {8, 16, 32, 64}")
     x = x.contiguous()
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        check(lib.wm_layernorm2d_fwd(_ptr(x), _ptr(_w(weight)), _ptr(_w(bias)), float(eps), _ptr(y), B, H * W, C,
-                                     _stream()), "wm_layernorm2d_fwd")
+    _launch(x.device, "wm_layernorm2d_fwd", x, _w(weight), _w(bias), float(eps), y, B, H * W, C)
     return y
 
 
@@ -646,9 +650,7 @@ def gram(x, y):
     ny = buf[B * C * (C + 1):].view(B, C)
     nws = int(lib.wm_gram_workspace_bytes(B, C, L))
     ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.wm_gram_fwd(_ptr(x), _ptr(y), _ptr(G), _ptr(nx), _ptr(ny), _ptr(ws), nws, B, C, L, _stream()),
-              "wm_gram_fwd")
+    _launch(x.device, "wm_gram_fwd", x, y, G, nx, ny, ws, nws, B, C, L)
     return G, nx, ny
 
 
@@ -697,7 +699,6 @@ class _DWConvTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, weight = ctx.saved_tensors
         gy = gy.contiguous().float()
         B, C, H, W = x.shape
@@ -705,9 +706,7 @@ class _DWConvTrain(torch.autograd.Function):
         buf = _zeros_small(10 * C, x.device)                                    # dW | db back to back, zeroed
         dW = buf[:9 * C].view(weight.shape)
         db = buf[9 * C:] if ctx.has_bias else None
-        with torch.cuda.device(x.device):
-            check(lib.wm_dwconv3x3_wgrad(_ptr(x.contiguous()), _ptr(gy), _ptr(dW), _ptr(db), B, C, H, W, _stream()),
-                  "wm_dwconv3x3_wgrad")
+        _launch(x.device, "wm_dwconv3x3_wgrad", x.contiguous(), gy, dW, db, B, C, H, W)
         return gx, dW, db
 
 
@@ -728,16 +727,13 @@ class _LayerNorm2dTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, weight = ctx.saved_tensors
         B, C, H, W = x.shape
         gy = gy.contiguous().float()
         gx = torch.empty_like(x)
         buf = _zeros_small(2 * C, x.device)                                     # dweight | dbias back to back, zeroed
         dw, db = buf[:C], buf[C:]
-        with torch.cuda.device(x.device):
-            check(lib.wm_layernorm2d_bwd(_ptr(x), _ptr(_w(weight)), _ptr(gy), ctx.eps, _ptr(gx), _ptr(dw), _ptr(db),
-                                         B, H * W, C, _stream()), "wm_layernorm2d_bwd")
+        _launch(x.device, "wm_layernorm2d_bwd", x, _w(weight), gy, ctx.eps, gx, dw, db, B, H * W, C)
         return gx, dw, db, None
 
 
@@ -751,29 +747,23 @@ class _LayerNormTok(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
-        lib = _lib.load()
         C = x.shape[-1]
-        w, b = weight.detach().contiguous().float(), bias.detach().contiguous().float()
+        w, b = _w(weight), _w(bias)
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib.wm_layernorm_tok_fwd(_ptr(x), _ptr(w), _ptr(b), float(eps), _ptr(y), x.numel() // C, C, _stream()),
-                  "wm_layernorm_tok_fwd")
+        _launch(x.device, "wm_layernorm_tok_fwd", x, w, b, float(eps), y, x.numel() // C, C)
         ctx.save_for_backward(x, w)
         ctx.eps = float(eps)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, w = ctx.saved_tensors
         C = x.shape[-1]
         gy = gy.contiguous().float()
         gx = torch.empty_like(x)
         buf = _zeros_small(2 * C, x.device)
         dw, db = buf[:C], buf[C:]
-        with torch.cuda.device(x.device):
-            check(lib.wm_layernorm_tok_bwd(_ptr(x), _ptr(w), _ptr(gy), ctx.eps, _ptr(gx), _ptr(dw), _ptr(db),
-                                           x.numel() // C, C, _stream()), "wm_layernorm_tok_bwd")
+        _launch(x.device, "wm_layernorm_tok_bwd", x, w, gy, ctx.eps, gx, dw, db, x.numel() // C, C)
         return gx, dw, db, None
 
 
@@ -816,27 +806,21 @@ class _Gate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, act):
-        lib = _lib.load()
         B, per_b = a.shape[0], a[0].numel()
         out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            check(lib.wm_gate_fwd(_ptr(a), _ptr(b), _ptr(out), act, B, per_b, a.stride(0), b.stride(0), out.stride(0) if B else 0,
-                                  _stream()), "wm_gate_fwd")
+        _launch(a.device, "wm_gate_fwd", a, b, out, act, B, per_b, a.stride(0), b.stride(0), out.stride(0) if B else 0)
         ctx.save_for_backward(a, b)
         ctx.act = act
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         a, b = ctx.saved_tensors
         g = g.contiguous().float()
         B, per_b = a.shape[0], a[0].numel()
         ga, gb = torch.empty_like(g), torch.empty_like(g)
-        with torch.cuda.device(a.device):
-            check(lib.wm_gate_bwd(_ptr(a), _ptr(b), _ptr(g), _ptr(ga), _ptr(gb), ctx.act, B, per_b, a.stride(0), b.stride(0),
-                                  g.stride(0) if B else 0, ga.stride(0) if B else 0, gb.stride(0) if B else 0, _stream()),
-                  "wm_gate_bwd")
+        _launch(a.device, "wm_gate_bwd", a, b, g, ga, gb, ctx.act, B, per_b, a.stride(0), b.stride(0),
+                g.stride(0) if B else 0, ga.stride(0) if B else 0, gb.stride(0) if B else 0)
         return ga, gb, None
 
 
@@ -846,35 +830,29 @@ class _GluGate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t, act):
-        lib = _lib.load()
         t = t.contiguous().float()
         B, C2 = t.shape[:2]
         C = C2 // 2
         per_b = C * t[0, 0].numel()
         out = torch.empty((B, C) + tuple(t.shape[2:]), dtype=torch.float32, device=t.device)
-        with torch.cuda.device(t.device):
-            check(lib.wm_gate_fwd(_ptr(t), t.data_ptr() + 4 * per_b, _ptr(out), act, B, per_b, 2 * per_b, 2 * per_b, per_b,
-                                  _stream()), "wm_gate_fwd")
+        _launch(t.device, "wm_gate_fwd", t, t.data_ptr() + 4 * per_b, out, act, B, per_b, 2 * per_b, 2 * per_b, per_b)
         ctx.save_for_backward(t)
         ctx.act = act
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         (t,) = ctx.saved_tensors
         g = g.contiguous().float()
         B, per_b = t.shape[0], g[0].numel()
         gt = torch.empty_like(t)
-        with torch.cuda.device(t.device):
-            check(lib.wm_gate_bwd(_ptr(t), t.data_ptr() + 4 * per_b, _ptr(g), _ptr(gt), gt.data_ptr() + 4 * per_b, ctx.act, B,
-                                  per_b, 2 * per_b, 2 * per_b, per_b, 2 * per_b, 2 * per_b, _stream()), "wm_gate_bwd")
+        _launch(t.device, "wm_gate_bwd", t, t.data_ptr() + 4 * per_b, g, gt, gt.data_ptr() + 4 * per_b, ctx.act, B,
+                per_b, 2 * per_b, 2 * per_b, per_b, 2 * per_b, 2 * per_b)
         return gt, None
 
 
 def glu_gate(t, act):
     """act(t[:, :C]) * t[:, C:] for a (B, 2C, H, W) fp32 tensor, act in {"silu", "gelu"}, differentiable (_GluGate)."""
-    _lib.load()
     _require_cuda("glu_gate", t)
     if t.dim() != 4 or t.shape[1] % 2 or t.shape[0] > 65535:
         raise NotImplementedError("glu_gate: a (B, 2C, H, W) tensor")
@@ -888,7 +866,6 @@ def gate_supported(a, b):
 
 def gate_act(a, b, act):
     """act(a) * b with act in {"silu", "gelu", "sigmoid"} (exact erf GELU), differentiable; see _Gate."""
-    _lib.load()
     _require_cuda("gate_act", a, b)
     if not gate_supported(a, b):
         raise NotImplementedError("gate_act: two fp32 (B, C, H, W) tensors, dense per batch item")
@@ -900,33 +877,28 @@ class _ScaleAdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, scale, o):
-        lib = _lib.load()
-        x, o, sc = x.contiguous().float(), o.contiguous().float(), scale.detach().contiguous().float()
+        x, o, sc = x.contiguous().float(), o.contiguous().float(), _w(scale)
         B, C = x.shape[:2]
         L = x[0, 0].numel()
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib.wm_scale_add_fwd(_ptr(x), _ptr(sc), _ptr(o), _ptr(out), B, C, L, _stream()), "wm_scale_add_fwd")
+        _launch(x.device, "wm_scale_add_fwd", x, sc, o, out, B, C, L)
         ctx.save_for_backward(x, sc)
         ctx.scale_shape = scale.shape
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, sc = ctx.saved_tensors
         g = g.contiguous().float()
         B, C = x.shape[:2]
         L = x[0, 0].numel()
         gx, gs = torch.empty_like(x), _zeros_small(C, x.device)
-        with torch.cuda.device(x.device):
-            check(lib.wm_scale_add_bwd(_ptr(g), _ptr(x), _ptr(sc), _ptr(gx), _ptr(gs), B, C, L, _stream()), "wm_scale_add_bwd")
+        _launch(x.device, "wm_scale_add_bwd", g, x, sc, gx, gs, B, C, L)
         return gx, gs.view(ctx.scale_shape), g
 
 
 def scale_add(x, scale, o):
     """x * scale.view(1, C, 1, 1) + o for (B, C, H, W) fp32 tensors and a C-element scale, differentiable."""
-    _lib.load()
     _require_cuda("scale_add", x, scale, o)
     if x.dim() != 4 or x.shape != o.shape or scale.numel() != x.shape[1] or x.shape[0] * x.shape[1] > 65535:
         raise NotImplementedError("scale_add: (B, C, H, W) operands with B C <= 65535 and a C-element scale")
@@ -940,7 +912,6 @@ def dwconv3x3(x, weight, bias=None, act="none", flip=False):
     """F.conv2d(x, weight, bias, stride=1, padding=1, groups=C) [+ SiLU / exact GELU when act == 'silu' / 'gelu'] for a
     (C, 1, 3, 3) weight, NCHW fp32 (or bf16 planes: fp32 arithmetic, bf16 storage), forward only (no autograd graph is
     recorded).  flip: with weight.flip(2, 3) - the convolution's input gradient - read from `weight` itself."""
-    lib = _lib.load()
     _require_cuda("dwconv3x3", x, weight, bias)
     B, C, H, W = x.shape
     if weight.shape != (C, 1, 3, 3):
@@ -948,42 +919,33 @@ def dwconv3x3(x, weight, bias=None, act="none", flip=False):
     code = _dtype_code(x, "dwconv3x3")
     x = x.contiguous()
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        check(lib.wm_dwconv3x3_fwd(_ptr(x), _ptr(weight.detach().contiguous().float()),
-                                   _ptr(None if bias is None else bias.detach().contiguous().float()), _ptr(y),
-                                   B, C, H, W, {"none": 0, "silu": 1, "gelu": 2}[act] + (4 if flip else 0), code, _stream()),
-              "wm_dwconv3x3_fwd")
+    _launch(x.device, "wm_dwconv3x3_fwd", x, _w(weight), None if bias is None else _w(bias), y,
+            B, C, H, W, {"none": 0, "silu": 1, "gelu": 2}[act] + (4 if flip else 0), code)
     return y
 
 
 def image_pre_u8(img, window_size=128, swap_rb=True):
     """(h, w, 3) uint8 device image -> (1, 3, Hp, Wp) fp32 in [0, 1], channel-major, reflect-padded to multiples of
     `window_size` (inference_wavemamba.py:99-105 + :28-36); swap_rb: BGR (cv2) -> RGB."""
-    lib = _lib.load()
     _require_cuda("image_pre_u8", img)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise RuntimeError(f"image_pre_u8: expected (h, w, 3) uint8, got {tuple(img.shape)} {img.dtype}")
     h, w = img.shape[:2]
     Hp, Wp = h + (window_size - h % window_size) % window_size, w + (window_size - w % window_size) % window_size
     out = torch.empty((1, 3, Hp, Wp), dtype=torch.float32, device=img.device)
-    with torch.cuda.device(img.device):
-        check(lib.wm_image_pre_u8(_ptr(img.contiguous()), _ptr(out), h, w, Hp, Wp, int(bool(swap_rb)), _stream()),
-              "wm_image_pre_u8")
+    _launch(img.device, "wm_image_pre_u8", img.contiguous(), out, h, w, Hp, Wp, int(bool(swap_rb)))
     return out
 
 
 def image_post_u8(t, h, w, swap_rb=True):
     """(1, 3, Hp, Wp) fp32 -> (h, w, 3) uint8: crop, clamp [0, 1], * 255, round half to even, channel-last
     (inference_wavemamba.py:112-113 + tensor2img, img_util.py:67-94); swap_rb: RGB -> BGR."""
-    lib = _lib.load()
     _require_cuda("image_post_u8", t)
     if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3:
         raise RuntimeError(f"image_post_u8: expected (1, 3, Hp, Wp) float32, got {tuple(t.shape)} {t.dtype}")
     Hp, Wp = t.shape[2:]
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=t.device)
-    with torch.cuda.device(t.device):
-        check(lib.wm_image_post_u8(_ptr(t.contiguous()), _ptr(out), h, w, Hp, Wp, int(bool(swap_rb)), _stream()),
-              "wm_image_post_u8")
+    _launch(t.device, "wm_image_post_u8", t.contiguous(), out, h, w, Hp, Wp, int(bool(swap_rb)))
     return out
 
 
@@ -1029,47 +991,37 @@ def psnr_ssim_y(a, b, crop_border=1, layout="HWC", bgr=True):
         raise RuntimeError(f"psnr_ssim_y: crop_border {crop} leaves nothing of a {H} x {W} image (needs 0 <= crop < min(H, W) / 2)")
     out = torch.empty((N, 2), dtype=torch.float64, device=va.device)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=va.device)
-    with torch.cuda.device(va.device):
-        check(lib.wm_psnr_ssim_y_u8(_ptr(va), _ptr(vb), *st, N, H, W, crop, int(bool(bgr)), _ptr(out), _ptr(ws), ws_bytes,
-                                    _stream()), "wm_psnr_ssim_y_u8")
+    _launch(va.device, "wm_psnr_ssim_y_u8", va, vb, *st, N, H, W, crop, int(bool(bgr)), out, ws, ws_bytes)
     return out
 
 
 def y_channel_u8(img, layout="HWC", bgr=True):
     """The reference's to_y_channel (comput_psnr_ssim.py:374-385, BT.601 Y in [16, 235], bit for bit) of uint8 CUDA images:
     (N, H, W, 3) / (N, 3, H, W) -> (N, H, W) float32, or (H, W) for one image without N."""
-    lib = _lib.load()
     (v,), N, H, W, st = _metric_images("y_channel_u8", layout, img)
     y = torch.empty((N, H, W), dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        check(lib.wm_y_channel_u8(_ptr(v), *st, N, H, W, int(bool(bgr)), _ptr(y), _stream()), "wm_y_channel_u8")
+    _launch(v.device, "wm_y_channel_u8", v, *st, N, H, W, int(bool(bgr)), y)
     return y if img.dim() == 4 else y[0]
 
 
 def match_index(G, nx, ny):
     """Channel matching with every channel kept: (B, C) int32 index of the L2-nearest candidate channel from the
     Gram outputs of `gram(maps, candidates)` (argmin_j |x_c|^2 + |y_j|^2 - 2 x_c . y_j)."""
-    lib = _lib.load()
     _require_cuda("match_index", G, nx, ny)
     B, C = nx.shape
     idx = torch.empty((B, C), dtype=torch.int32, device=G.device)
-    with torch.cuda.device(G.device):
-        check(lib.wm_match_index(_ptr(G.contiguous()), _ptr(nx.contiguous()), _ptr(ny.contiguous()), _ptr(idx), B, C,
-                                 _stream()), "wm_match_index")
+    _launch(G.device, "wm_match_index", G.contiguous(), nx.contiguous(), ny.contiguous(), idx, B, C)
     return idx
 
 
 def attn_fold(G, nq, nk, temperature, w_po, batch, heads):
     """(batch, C, C) = w_po @ blockdiag_h softmax(G / (|q||k|) * temperature): the transposed attention folded into its
     1x1 output projection.  G (batch * heads, ch, ch), nq / nk (batch * heads, ch) squared norms."""
-    lib = _lib.load()
     _require_cuda("attn_fold", G, nq, nk, temperature, w_po)
     C = w_po.shape[0]
     out = torch.empty((batch, C, C), dtype=torch.float32, device=G.device)
-    with torch.cuda.device(G.device):
-        check(lib.wm_attn_fold(_ptr(G.contiguous()), _ptr(nq.contiguous()), _ptr(nk.contiguous()),
-                               _ptr(temperature.detach().contiguous()), _ptr(w_po.detach().reshape(C, C).contiguous()),
-                               _ptr(out), batch, C, heads, _stream()), "wm_attn_fold")
+    _launch(G.device, "wm_attn_fold", G.contiguous(), nq.contiguous(), nk.contiguous(), temperature.detach().contiguous(),
+            w_po.detach().reshape(C, C).contiguous(), out, batch, C, heads)
     return out
 
 
@@ -1084,14 +1036,9 @@ def skff(x0, x1, x2, w_du, prelu, w_fc):
     x0, x1, x2 = x0.contiguous(), x1.contiguous(), x2.contiguous()
     out = torch.empty_like(x0)
     ws = torch.empty(lib.wm_skff_workspace_bytes(B, C), dtype=torch.uint8, device=x0.device)
-    with torch.cuda.device(x0.device):
-        check(lib.wm_skff_fwd(_ptr(x0), _ptr(x1), _ptr(x2), _ptr(w_du.detach().reshape(d, C).contiguous()),
-                              _ptr(prelu.detach().contiguous()), _ptr(w_fc.detach().reshape(3, C, d).contiguous()),
-                              _ptr(out), _ptr(ws), ws.numel(), B, C, d, H, W, _stream()), "wm_skff_fwd")
+    _launch(x0.device, "wm_skff_fwd", x0, x1, x2, w_du.detach().reshape(d, C).contiguous(), prelu.detach().contiguous(),
+            w_fc.detach().reshape(3, C, d).contiguous(), out, ws, ws.numel(), B, C, d, H, W)
     return out
-
-
-_WFRAG_CACHE = {}      # id(weight) -> (weakref, data_ptr, version, wfrag tensor, prep-done event, stream it was built on)
 
 
 CONV3X3_AUTO, CONV3X3_FIRST_GEN, CONV3X3_WAVE_SPECIALISED = 0, 1, 2
@@ -1119,34 +1066,38 @@ def _conv2d_wfrag(weight, cache=True):
     (the folded attention), prepared every time.  A cached copy built on another stream is waited for (event) and
     recorded on the using stream, so multi-stream serving never reads it before the preparation kernel has finished
     nor sees it freed under a pending launch."""
-    import weakref
-    key = id(weight)
-    cur = torch.cuda.current_stream(weight.device)
-    ent = _WFRAG_CACHE.get(key) if cache else None
-    if ent is not None and ent[0]() is weight and ent[1] == weight.data_ptr() and ent[2] == weight._version:
-        if ent[5] != cur.cuda_stream:
-            if torch.cuda.is_current_stream_capturing():
-                # an event recorded outside the capture cannot be waited for inside it: block the HOST until the producer
-                # (a warm-up forward on another stream that was never joined) is done - then the fragments are simply there
-                _host_wait_under_capture(ent[4])
-            else:
-                cur.wait_event(ent[4])
-                ent[3].record_stream(cur)
-        return ent[3]
-    lib = _lib.load()
+    frag = _WFRAG_CACHE.get((weight,)) if cache else None
+    if frag is not None:
+        return frag
     cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
-    frag = torch.empty(lib.wm_conv2d_wfrag_bytes(cout, cin, ks), dtype=torch.uint8, device=weight.device)
-    with torch.cuda.device(weight.device):
-        check(lib.wm_conv2d_prep(_ptr(weight.detach().contiguous()), _ptr(frag), cout, cin, ks, _stream()),
-              "wm_conv2d_prep")
-    if cache and torch.cuda.is_current_stream_capturing():
-        return frag                                   # prepared inside the capture: part of the graph, not of the cache
-    if cache:
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        _WFRAG_CACHE[key] = (weakref.ref(weight, lambda _r, k=key: _WFRAG_CACHE.pop(k, None)), weight.data_ptr(),
-                             weight._version, frag, ev, cur.cuda_stream)
+    frag = torch.empty(_lib.load().wm_conv2d_wfrag_bytes(cout, cin, ks), dtype=torch.uint8, device=weight.device)
+    _launch(weight.device, "wm_conv2d_prep", weight.detach().contiguous(), frag, cout, cin, ks)
+    if cache and not torch.cuda.is_current_stream_capturing():   # prepared inside a capture: part of the graph, not of the cache
+        _WFRAG_CACHE.put((weight,), frag)
     return frag
+
+
+def _conv_operands(name, expects, x, x2, x2_index, weights):
+    """The input X of `conv2d` / `conv2d_gated` = x, cat([x, x2], 1) or cat([x, gather(x2, 1, x2_index)], 1), checked against
+    the (Cout, Cin, ...) `weights` (all float32) -> (x, x2, int32 index, cb, cb_src), contiguous, for the kernels' argument lists:
+    cb channels of X come from x2, which has cb_src."""
+    B, Ca, H, W = x.shape
+    cin = weights[0].shape[1]
+    cb = cb_src = 0
+    if x2 is not None:
+        if (x2.shape[0], x2.shape[2], x2.shape[3]) != (B, H, W):
+            raise RuntimeError(f"{name}: x2 {tuple(x2.shape)} does not match x {tuple(x.shape)}")
+        cb_src = x2.shape[1]
+        cb = cb_src if x2_index is None else x2_index.shape[1]
+        if x2_index is not None and (x2_index.shape[0] != B or x2_index.dim() != 2):
+            raise RuntimeError(f"{name}: x2_index must be (B, Cb), got {tuple(x2_index.shape)}")
+    if cin != Ca + cb:
+        raise RuntimeError(f"{name}: {expects} {cin} input channels, got {Ca} + {cb}")
+    for t in (x, *weights, x2):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: float32 only")
+    return (x.contiguous(), None if x2 is None else x2.contiguous(),
+            None if x2_index is None else x2_index.to(torch.int32).contiguous(), cb, cb_src)
 
 
 def conv2d(x, weight, bias=None, x2=None, x2_index=None, gate=None, residual=None, dynamic_weight=False):
@@ -1155,39 +1106,24 @@ def conv2d(x, weight, bias=None, x2=None, x2_index=None, gate=None, residual=Non
     (B, Cb) channel indices into x2; then y *= sigmoid(gate) and y += residual when given.  Forward only (no
     autograd graph is recorded).  bf16 matrix cores with a two-term split of both operands: 3-4e-6 relative to
     the fp64 result.  dynamic_weight: `weight` is a freshly computed tensor (no prepared-copy cache)."""
-    lib = _lib.load()
     _require_cuda("conv2d", x, weight, bias, x2, x2_index, gate, residual)
     B, Ca, H, W = x.shape
-    cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
+    cout, ks = weight.shape[0], weight.shape[2]
     if weight.dim() != 4 or weight.shape[3] != ks or ks not in (1, 3):
         raise RuntimeError(f"conv2d: weight must be (Cout, Cin, ks, ks) with ks in (1, 3), got {tuple(weight.shape)}")
-    cb = cb_src = 0
-    if x2 is not None:
-        if (x2.shape[0], x2.shape[2], x2.shape[3]) != (B, H, W):
-            raise RuntimeError(f"conv2d: x2 {tuple(x2.shape)} does not match x {tuple(x.shape)}")
-        cb_src = x2.shape[1]
-        cb = cb_src if x2_index is None else x2_index.shape[1]
-        if x2_index is not None and (x2_index.shape[0] != B or x2_index.dim() != 2):
-            raise RuntimeError(f"conv2d: x2_index must be (B, Cb), got {tuple(x2_index.shape)}")
-    if cin != Ca + cb:
-        raise RuntimeError(f"conv2d: weight expects {cin} input channels, got {Ca} + {cb}")
-    for t in (x, weight, x2, gate, residual):
+    x, x2, idx, cb, cb_src = _conv_operands("conv2d", "weight expects", x, x2, x2_index, (weight,))
+    for t in (gate, residual):
         if t is not None and t.dtype != torch.float32:
             raise RuntimeError("conv2d: float32 only")
     for t, name in ((gate, "gate"), (residual, "residual")):
         if t is not None and tuple(t.shape) != (B, cout, H, W):
             raise RuntimeError(f"conv2d: {name} must be {(B, cout, H, W)}, got {tuple(t.shape)}")
-    x = x.contiguous()
-    x2 = None if x2 is None else x2.contiguous()
-    idx = None if x2_index is None else x2_index.to(torch.int32).contiguous()
     gate = None if gate is None else gate.contiguous()
     residual = None if residual is None else residual.contiguous()
     frag = _conv2d_wfrag(weight, cache=not dynamic_weight)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.wm_conv2d_fwd(_ptr(x), _ptr(x2), _ptr(idx), _ptr(frag),
-                                _ptr(None if bias is None else bias.detach().contiguous()), _ptr(gate), _ptr(residual),
-                                _ptr(y), B, Ca, cb, cb_src, cout, H, W, ks, _stream()), "wm_conv2d_fwd")
+    _launch(x.device, "wm_conv2d_fwd", x, x2, idx, frag, None if bias is None else bias.detach().contiguous(), gate, residual, y,
+            B, Ca, cb, cb_src, cout, H, W, ks)
     return y
 
 
@@ -1231,16 +1167,13 @@ def conv2d_f16(x, weight, bias=None, dgrad=False):
     wfrag = torch.empty(nws - 256, dtype=torch.uint8, device=x.device)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     b = None if bias is None else bias.detach().contiguous()
-    with torch.cuda.device(x.device):
-        check(lib.wm_conv2d_f16_steps(_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(amax), _ptr(wfrag), B, cin, cout, H, W, ks,
-                                      1 if dgrad else 0, _stream()), "wm_conv2d_f16_steps")
+    _launch(x.device, "wm_conv2d_f16_steps", x, w, b, y, amax, wfrag, B, cin, cout, H, W, ks, 1 if dgrad else 0)
     return y
 
 
 def conv2d_ln(x, ln_weight, ln_bias, ln_eps, weight, bias=None, residual=None):
     """conv1x1(LayerNorm2d(x)) + bias (+ residual) in one kernel (wm_conv2d_ln_fwd): x (B, 32, H, W) fp32, weight (Cout, 32, 1, 1).
     Bit-identical to layernorm2d() + conv2d().  Forward only."""
-    lib = _lib.load()
     _require_cuda("conv2d_ln", x, ln_weight, ln_bias, weight, bias, residual)
     B, C, H, W = x.shape
     cout = weight.shape[0]
@@ -1251,11 +1184,9 @@ def conv2d_ln(x, ln_weight, ln_bias, ln_eps, weight, bias=None, residual=None):
     x = x.contiguous()
     frag = _conv2d_wfrag(weight)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.wm_conv2d_ln_fwd(_ptr(x), _ptr(_w(ln_weight)), _ptr(_w(ln_bias)), float(ln_eps), _ptr(frag),
-                                   _ptr(None if bias is None else bias.detach().contiguous()),
-                                   _ptr(None if residual is None else residual.contiguous()), _ptr(y), B, C, cout, H, W, _stream()),
-              "wm_conv2d_ln_fwd")
+    _launch(x.device, "wm_conv2d_ln_fwd", x, _w(ln_weight), _w(ln_bias), float(ln_eps), frag,
+            None if bias is None else bias.detach().contiguous(), None if residual is None else residual.contiguous(), y,
+            B, C, cout, H, W)
     return y
 
 
@@ -1273,7 +1204,6 @@ def patchify_conv(img, weight, bias, r):
     """conv1x1(pixel_unshuffle(img, r)) (the UNet's ps_down1..3, reference wavemamba_arch.py:1014-1025 / :1043-1045) as one
     r x r / stride-r convolution read straight from the image: the unshuffled tensor is never materialised.  Forward only.
     img (B, Cin, H, W) fp32; weight (Cout, Cin r r, 1, 1); bias (Cout) or None -> (B, Cout, H / r, W / r) fp32."""
-    lib = _lib.load()
     _require_cuda("patchify_conv", img, weight)
     if not patchify_conv_supported(img, weight, r):
         raise ValueError("patchify_conv: unsupported shapes (see patchify_conv_supported)")
@@ -1281,9 +1211,7 @@ def patchify_conv(img, weight, bias, r):
     B, Cin, H, W = img.shape
     Cout = weight.shape[0]
     y = torch.empty((B, Cout, H // r, W // r), dtype=torch.float32, device=img.device)
-    with torch.cuda.device(img.device):
-        check(lib.wm_patchify_conv_fwd(_ptr(img), _ptr(_w(weight)), None if bias is None else _ptr(_w(bias)), _ptr(y), B, Cin, Cout,
-                                       H, W, r, _stream()), "wm_patchify_conv_fwd")
+    _launch(img.device, "wm_patchify_conv_fwd", img, _w(weight), None if bias is None else _w(bias), y, B, Cin, Cout, H, W, r)
     return y
 
 
@@ -1296,33 +1224,17 @@ def conv2d_gated(x, weight3, weight1, bias1=None, x2=None, x2_index=None):
     """conv3x3(X; weight3) * sigmoid(conv1x1(X; weight1) + bias1) with X as in `conv2d` - PAConv's k3(x) * sigmoid(k2(x))
     (reference wavemamba_arch.py:694-697) in one kernel.  weight3 (Cout, Cin, 3, 3) without bias, weight1
     (Cout, Cin, 1, 1).  Forward only."""
-    lib = _lib.load()
     _require_cuda("conv2d_gated", x, weight3, weight1, bias1, x2, x2_index)
     B, Ca, H, W = x.shape
     cout, cin = weight3.shape[0], weight3.shape[1]
     if tuple(weight3.shape) != (cout, cin, 3, 3) or tuple(weight1.shape) != (cout, cin, 1, 1):
         raise RuntimeError(f"conv2d_gated: weights must be (Cout, Cin, 3, 3) and (Cout, Cin, 1, 1), got "
                            f"{tuple(weight3.shape)} and {tuple(weight1.shape)}")
-    cb = cb_src = 0
-    if x2 is not None:
-        if (x2.shape[0], x2.shape[2], x2.shape[3]) != (B, H, W):
-            raise RuntimeError(f"conv2d_gated: x2 {tuple(x2.shape)} does not match x {tuple(x.shape)}")
-        cb_src = x2.shape[1]
-        cb = cb_src if x2_index is None else x2_index.shape[1]
-    if cin != Ca + cb:
-        raise RuntimeError(f"conv2d_gated: weights expect {cin} input channels, got {Ca} + {cb}")
-    for t in (x, weight3, weight1, x2):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError("conv2d_gated: float32 only")
-    x = x.contiguous()
-    x2 = None if x2 is None else x2.contiguous()
-    idx = None if x2_index is None else x2_index.to(torch.int32).contiguous()
+    x, x2, idx, cb, cb_src = _conv_operands("conv2d_gated", "weights expect", x, x2, x2_index, (weight3, weight1))
     f3, f1 = _conv2d_wfrag(weight3), _conv2d_wfrag(weight1)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.wm_conv2d_gated_fwd(_ptr(x), _ptr(x2), _ptr(idx), _ptr(f3), _ptr(f1),
-                                      _ptr(None if bias1 is None else bias1.detach().contiguous()), _ptr(y),
-                                      B, Ca, cb, cb_src, cout, H, W, _stream()), "wm_conv2d_gated_fwd")
+    _launch(x.device, "wm_conv2d_gated_fwd", x, x2, idx, f3, f1, None if bias1 is None else bias1.detach().contiguous(), y,
+            B, Ca, cb, cb_src, cout, H, W)
     return y
 
 
@@ -1340,7 +1252,6 @@ class _LinearNoBias(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        lib = _lib.load()
         x, weight = ctx.saved_tensors
         gx = gw = None
         if ctx.needs_input_grad[0]:
@@ -1349,8 +1260,7 @@ class _LinearNoBias(torch.autograd.Function):
             O, I = weight.shape
             g2, x2 = gy.reshape(-1, O).contiguous().float(), x.reshape(-1, I).contiguous().float()
             gw = _zeros_small(O * I, x.device).view(O, I)
-            with torch.cuda.device(x.device):
-                check(lib.wm_linear_wgrad(_ptr(g2), _ptr(x2), _ptr(gw), g2.shape[0], O, I, _stream()), "wm_linear_wgrad")
+            _launch(x.device, "wm_linear_wgrad", g2, x2, gw, g2.shape[0], O, I)
         return gx, gw
 
 
@@ -1367,13 +1277,11 @@ def linear_nobias(x, weight):
 
 def plane_sums(x):
     """x (B, C, H, W) fp32 -> (C,) sums over batch and plane (bias gradient of a convolution)."""
-    lib = _lib.load()
     _require_cuda("plane_sums", x)
     B, C, H, W = x.shape
     x = x.contiguous().float()
     out = _zeros_small(C, x.device)
-    with torch.cuda.device(x.device):
-        check(lib.wm_plane_sums(_ptr(x), _ptr(out), B, C, H, W, _stream()), "wm_plane_sums")
+    _launch(x.device, "wm_plane_sums", x, out, B, C, H, W)
     return out
 
 
@@ -1385,21 +1293,17 @@ class _L1Mean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b):
-        lib = _lib.load()
         ctx.save_for_backward(a, b)
         out = _zeros_small(1, a.device)
-        with torch.cuda.device(a.device):
-            check(lib.wm_l1_mean_fwd(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "wm_l1_mean_fwd")
+        _launch(a.device, "wm_l1_mean_fwd", a, b, out, a.numel())
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         a, b = ctx.saved_tensors
         g = g.contiguous().float()
         ga = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            check(lib.wm_l1_mean_bwd(_ptr(a), _ptr(b), _ptr(g), _ptr(ga), a.numel(), _stream()), "wm_l1_mean_bwd")
+        _launch(a.device, "wm_l1_mean_bwd", a, b, g, ga, a.numel())
         return (ga if ctx.needs_input_grad[0] else None), (-ga if ctx.needs_input_grad[1] else None)
 
 
@@ -1476,8 +1380,7 @@ def conv2d_wgrad(gy, x, ks, _refusal=RuntimeError, with_bias=False):
     ws = torch.empty(need, dtype=torch.uint8, device=x.device)
     dW = torch.empty(Cout, Cin, ks, ks, dtype=torch.float32, device=x.device)
     db = torch.empty(Cout, dtype=torch.float32, device=x.device) if with_bias else None
-    with torch.cuda.device(x.device):
-        rc = lib.wm_conv2d_wgrad(_ptr(gy), _ptr(x), _ptr(dW), _ptr(db), _ptr(ws), need, B, Cin, Cout, H, W, ks, _stream())
+    rc = _launch(x.device, "wm_conv2d_wgrad", gy, x, dW, db, ws, need, B, Cin, Cout, H, W, ks, status=True)
     if rc in (_lib.WM_EUNSUPPORTED, _lib.WM_EALIGN) and _refusal is not RuntimeError:
         raise _refusal(f"wm_conv2d_wgrad refused the call (code {rc})")
     check(rc, "wm_conv2d_wgrad")
