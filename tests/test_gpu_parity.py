@@ -285,6 +285,7 @@ def test_scan_backward_golden(golden, tag):
     (2, 96, 77, 16, 1),          # 96 channels per group: two waves per group (atomic dB/dC), L % 4 != 0
     (1, 40, 50, 7, 4),           # 10 channels per group, N = 7
     (1, 8, 1, 4, 2),             # L = 1
+    (1, 64, 45, 32, 2),          # d_state 32 on the element-wise path (L % 4 != 0): three chunks, the last one ragged
 ])
 def test_scan_backward_vs_oracle(batch, dim, L, N, G):
     """du / ddelta / dB / dC against the CPU oracle at 1e-4.  dA / dD / dbias are sums over batch and L of products of

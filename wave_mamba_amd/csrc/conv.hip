@@ -125,8 +125,8 @@ int wm_conv2d_prep(const float* weight, void* wfrag, int Cout, int Cin, int ks, 
     if (!aligned16(wfrag)) return WM_EALIGN;
     const int nch = (Cin + 15) / 16, mtot = (Cout + 31) / 32;
     const long long total = (long long)nch * ks * ks * mtot * 128;
-    hipLaunchKernelGGL(conv2d_prep_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       weight, (uint4*)wfrag, Cout, Cin, ks * ks, nch, mtot, (const float*)nullptr);
+    hipLaunchKernelGGL(conv2d_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       weight, (uint4*)wfrag, Cout, Cin, ks * ks, nch, mtot);
     return launch_status();
 }
 

@@ -139,14 +139,12 @@ __device__ __forceinline__ void cv_prep_item(const float* __restrict__ w, uint4*
 // w (Cout, Cin, KS, KS) fp32 -> wfrag[chunk][tap][m][split][lane] x 8 bf16: lane l of fragment (chunk, tap, m)
 // holds w[32 m + (l & 31)][16 chunk + 8 (l >> 5) + j][tap], j = 0..7 (the A-operand layout of
 // v_mfma_f32_32x32x16_bf16); channels beyond Cout / Cin are zero.
-template <bool F16 = false>
+// (The fp16 fragments and the input-gradient form are cv_amax_prep_kernel's.)
 __global__ __launch_bounds__(256) void conv2d_prep_kernel(const float* __restrict__ w, uint4* __restrict__ wfrag,
-                                                          int Cout, int Cin, int taps, int nch, int mtot,
-                                                          const float* __restrict__ amax = nullptr, int dgrad = 0) {
-    const float sw = F16 ? cv_pow2_scale(amax[1]) : 1.0f;
+                                                          int Cout, int Cin, int taps, int nch, int mtot) {
     const long long total = (long long)nch * taps * mtot * 2 * 64;
     for (long long idx = blockIdx.x * 256ll + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256)
-        cv_prep_item<F16>(w, wfrag, idx, Cout, Cin, taps, mtot, sw, dgrad);
+        cv_prep_item<false>(w, wfrag, idx, Cout, Cin, taps, mtot, 1.0f, 0);
 }
 
 // Operand magnitudes + weight preparation of the training step's fp16-split convolutions (88 per BASELINE config-3 step) in ONE launch

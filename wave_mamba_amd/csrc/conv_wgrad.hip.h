@@ -122,13 +122,10 @@ __global__ __launch_bounds__(64 * kCwWaves, WM_CW_WAVES_PER_SIMD) void conv_wgra
             for (int ky = 0; ky < KS; ++ky) load_row(xp, h + ky - PAD, w, r.x[ky]);
         }
     };
-#ifndef WM_CW_PREFETCH
-#define WM_CW_PREFETCH 0
-#endif
+    // (fetching unit u + 1 before unit u's products changed nothing: profiles/history/DESIGN_rounds_1_to_5.md, conv wgrad)
     Raw cur, nxt;
     if (u_begin < u_end) fetch(u_begin, cur, cur, false);
     for (int u = u_begin; u < u_end; ++u) {
-        if (WM_CW_PREFETCH && u + 1 < u_end) fetch(u + 1, nxt, cur, (u + 1) % a.H != 0);   // uniform
         const int h = u % a.H;
         const int w = 32 * ((u / a.H) % segs) + 8 * kq;
         // gy tiles -> bf16 hi / lo (rows beyond the launch's output channels: zero)
@@ -181,8 +178,7 @@ __global__ __launch_bounds__(64 * kCwWaves, WM_CW_WAVES_PER_SIMD) void conv_wgra
                         acc[o][ky * KS + kx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                             term == 0 ? gl[o] : gh[o], term == 1 ? xl[kx] : xh[kx], acc[o][ky * KS + kx], 0, 0, 0);
         }
-        if (WM_CW_PREFETCH) cur = nxt;
-        else if (u + 1 < u_end) { nxt = cur; fetch(u + 1, cur, nxt, (u + 1) % a.H != 0); }
+        if (u + 1 < u_end) { nxt = cur; fetch(u + 1, cur, nxt, (u + 1) % a.H != 0); }   // uniform
     }
     // D layout: lane holds rows 4 kq .. 4 kq + 3 (co within the tile) of column i16 (ci within the tile).  Every wave
     // writes its own partial (no sums across waves: bit-reproducible).

@@ -104,17 +104,16 @@ static int bwd_launch(const ScanBwdArgs& a0, const BwdPlan& pl, float* seg, floa
     const dim3 grid((unsigned)pl.nblocks, (unsigned)pl.rows), block(64);
     ProfScope ps(12, st);
     if (pl.nchunks > 1) {
-        hipLaunchKernelGGL((selscan_bwd_reduce_kernel<NP, VEC, 0>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((selscan_bwd_reduce_kernel<NP, VEC>), grid, block, 0, st, a);
         if (pl.nblocks > 1) bwd_launch_carry(a, pl, seg, st);
     }
-    hipLaunchKernelGGL((selscan_bwd_chunk_kernel<NP, VEC, 0>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((selscan_bwd_chunk_kernel<NP, VEC>), grid, block, 0, st, a);
     zero_async(dA, (size_t)a.dim * a.N * sizeof(float), st);
     if (dD) zero_async(dD, (size_t)a.dim * sizeof(float), st);
     if (dbias) zero_async(dbias, (size_t)a.dim * sizeof(float), st);
     const int ysplit = bwd_finish_split(pl.nblocks, NP + kPartPad);
     hipLaunchKernelGGL(selscan_bwd_finish_kernel, dim3((unsigned)a.dim, (unsigned)ysplit), dim3(256), 0, st,
-                       (const float*)a.part, dA, dD, dbias, a.batch, a.dim, a.N, NP + kPartPad, pl.nblocks,
-                       (const float*)nullptr, (float*)nullptr, 0, NP);
+                       (const float*)a.part, dA, dD, dbias, a.batch, a.dim, a.N, NP + kPartPad, pl.nblocks, NP);
     return launch_status();
 }
 
@@ -285,7 +284,7 @@ int wm_selscan_bwd(const float* u, const float* delta, const float* A, const flo
     float* seg = nullptr;
     bwd_bind_workspace(a, pl, (char*)workspace, seg);
     a.batch = batch; a.dim = dim; a.L = L; a.N = N; a.G = G; a.dpg = dim / G; a.wpg = pl.wpg;
-    a.softplus = delta_softplus ? 1 : 0; a.atomic_bc = pl.wpg > 1 ? 1 : 0; a.accumulate = 0;
+    a.softplus = delta_softplus ? 1 : 0; a.atomic_bc = pl.wpg > 1 ? 1 : 0;
     if (a.atomic_bc) {
         const size_t nb = (size_t)batch * G * N * L * sizeof(float);
         hipError_t e = zero_async(dB, nb, st);

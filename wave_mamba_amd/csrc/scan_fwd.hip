@@ -157,10 +157,9 @@ static int core_plan(CorePlan& pl, int B, int D, int H, int W, int N, int R, int
     const long long L = (long long)H * W;
     if (L * D > 0x7fffffffLL) return WM_EUNSUPPORTED;          // 32-bit element offsets inside one batch item
     pl.NP = N <= 16 ? 16 : 32;
+    // (12-wave and 8-wave workgroups at N <= 16 were measured slower or equal at every UHD level:
+    // profiles/r04/core_forward_experiments.txt, profiles/r06/core_forward_analysis.md item 8)
     pl.NW = pl.NP == 16 ? 16 : 8;
-#ifdef WM_CORE_NW
-    if (pl.NP == 16) pl.NW = WM_CORE_NW;
-#endif
     const int NW = pl.NW;
     pl.col_tiles = (W + NW - 1) / NW;
     // Work split.  Column workgroups: one per (NW-column tile, segment of `col_seg` rows); row workgroups: NW waves with
@@ -433,13 +432,10 @@ int wm_ss2d_core_fwd(const void* x, const float* x_proj_weight, const float* dt_
         a.dirmask = mask;
     }
     a.col_seg = pl.col_seg; a.col_nseg = pl.col_nseg; a.col_tiles = pl.col_tiles; a.col_wgs = pl.col_wgs;
-#ifndef WM_CORE_NW
-#define WM_CORE_NW 16
-#endif
 #define WM_CORE_GO(TP, VEC)                                                                                                   \
     do {                                                                                                                      \
         const bool dp = prepared == nullptr;                                                                                  \
-        if (pl.NP == 16) rc = R > 2 ? core_launch<16, WM_CORE_NW, true, TP, VEC>(a, pl, dp, st) : core_launch<16, WM_CORE_NW, false, TP, VEC>(a, pl, dp, st); \
+        if (pl.NP == 16) rc = R > 2 ? core_launch<16, 16, true, TP, VEC>(a, pl, dp, st) : core_launch<16, 16, false, TP, VEC>(a, pl, dp, st); \
         else rc = R > 2 ? core_launch<32, 8, true, TP, VEC>(a, pl, dp, st) : core_launch<32, 8, false, TP, VEC>(a, pl, dp, st); \
     } while (0)
     if (!vec) WM_CORE_GO(float, false);

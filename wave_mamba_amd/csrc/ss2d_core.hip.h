@@ -41,17 +41,10 @@
 #include "selscan.hip.h"
 #include "haar.hip.h"          // bf16_t and its conversions
 
-#ifndef WM_CORE_ABLATE
-#define WM_CORE_ABLATE 0          // timing experiments only (wrong results): 1 = no MFMA, 2 = no scan steps, 4 = no y store
-#endif
+// (Ablation builds of this kernel - no projection / no scan steps / no y store, wrong results, timing only - were measured in
+// round 3: profiles/r03/core_ab_bench_core.txt.)
 #ifndef WM_CORE_STAMP
 #define WM_CORE_STAMP 0           // diagnostics: per-wave s_memtime phase totals into CoreArgs::stamps (tools/core_stamps.py)
-#endif
-#ifndef WM_CORE_ROW_SYNC
-#define WM_CORE_ROW_SYNC 0        // row directions: workgroup barrier every this many tiles (0 = never), see core_body
-#endif
-#ifndef WM_CORE_STEP_FENCE
-#define WM_CORE_STEP_FENCE 1      // scheduling barrier after every scan step
 #endif
 
 namespace wm {
@@ -118,11 +111,10 @@ template <int NP> struct CoreCfg {
     static constexpr int P_W3 = P_LC + 6 * 64;
     static constexpr int PREP = P_W3 + 512;
 };
-#ifndef WM_CORE_LDS_PAD
-#define WM_CORE_LDS_PAD 0         // experiments: extra dynamic LDS per workgroup (bytes), e.g. to keep a second workgroup off the compute unit
-#endif
+// (Padding this with 16 KB to keep a second 8-wave workgroup off the compute unit was measured slower in round 4:
+// profiles/r04/core_forward_experiments.txt.)
 template <int NP, int NW> constexpr int core_lds_bytes() {
-    return (CoreCfg<NP>::WF + NW * CoreCfg<NP>::XT + NW * 16 * CoreCfg<NP>::RS + 4 /* row-chunk counter */) * 4 + WM_CORE_LDS_PAD;
+    return (CoreCfg<NP>::WF + NW * CoreCfg<NP>::XT + NW * 16 * CoreCfg<NP>::RS + 4 /* row-chunk counter */) * 4;
 }
 
 typedef __bf16 core_bf2 __attribute__((ext_vector_type(2)));
@@ -477,9 +469,8 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
             // order) of tile column c16, split into bf16 hi / lo.  Channels >= D: zero-filled tile rows, zero weights.
             {
                 const uint4* sw4 = reinterpret_cast<const uint4*>(s_w) + lane;
-                constexpr int S2 = (WM_CORE_ABLATE & 1) ? 0 : 2;
 #pragma unroll
-                for (int s2 = 0; s2 < S2; ++s2) {
+                for (int s2 = 0; s2 < 2; ++s2) {
                     float xf[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) xf[j] = sx[(32 * s2 + 4 * j + g4) * ROW + c16];
@@ -525,7 +516,7 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
             // SGPR and copies it to a VGPR for its ds_read.  One opaque per-lane base per quad + compile-time offsets
             // puts them in the instructions' offset fields instead.
 #pragma unroll 1
-            for (int q = 0; q < ((WM_CORE_ABLATE & 2) ? 0 : 4); ++q) {
+            for (int q = 0; q < 4; ++q) {
                 if (q == 1 && ti + 1 < ntiles) fetch(ti + 1);            // uniform; see the note at the top of the tile loop
                 const int cq = REV ? 3 - q : q;
                 const float4 u4 = *reinterpret_cast<const float4*>(&sx[lane * ROW + 4 * cq]);
@@ -573,18 +564,16 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
                         }
                         if (PHASE == 3)      // y overwrites the consumed u (same lane, same row)
                             sx[lane * ROW + 4 * cq + (REV ? 3 - j : j)] = fmaf(Dd, ut, y2.x + y2.y);
-#if WM_CORE_STEP_FENCE == 1
-                        __builtin_amdgcn_sched_barrier(0);   // keep the next step's record reads out of this step's registers
-#elif WM_CORE_STEP_FENCE == 2
-                        if (jj == 1) __builtin_amdgcn_sched_barrier(0);      // ... per pair of steps
-#endif
+                        // keep the next step's record reads out of this step's registers (a fence per pair of steps, or none,
+                        // was no faster: profiles/r06/core_forward_analysis.md item 7)
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             }
         }
 
         WM_STAMP(3)                                      // 16 scan steps
-        if (PHASE == 3 && !(WM_CORE_ABLATE & 4)) {
+        if (PHASE == 3) {
             if (!COL) {
                 core_lds_fence();
 #pragma unroll
@@ -623,10 +612,7 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
         WM_STAMP(4)                                      // y store (+ barriers)
         // Row directions need no barrier (wave-private tiles).  Free-running, the four waves of a SIMD drift apart (the
         // scheduler favours the oldest: wave lifetimes 500 .. 1,150 us inside one workgroup, tools/core_stamps.py), but
-        // bounding the drift with a barrier every 1 / 2 / 4 tiles changed the launch time by < 1 %: off by default.
-        // (Waves that have ended - shorter last chunk, no chunk at all - no longer count towards s_barrier.)
-        if (!COL && WM_CORE_ROW_SYNC > 0 && (ti % (WM_CORE_ROW_SYNC > 0 ? WM_CORE_ROW_SYNC : 1)) == WM_CORE_ROW_SYNC - 1)
-            core_barrier();
+        // bounding the drift with a barrier every 1 / 2 / 4 tiles changed the launch time by < 1 %: there is none.
     }
 #if WM_CORE_STAMP == 2
     if (lane == 0 && p.stamps) {          // light mode: workgroup entry / exit only (no per-phase accumulators, no scratch)

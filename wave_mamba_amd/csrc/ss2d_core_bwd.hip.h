@@ -26,16 +26,6 @@
 #include "selscan_bwd.hip.h"
 #include "ss2d_core.hip.h"
 
-#ifndef WM_BWD_MFMA_NOP
-#define WM_BWD_MFMA_NOP 1        // wait states between a chain of matrix instructions and the first VALU / LDS use of its result
-#endif
-#ifndef WM_BWD_DX_LATE
-#define WM_BWD_DX_LATE 0         // experiment: keep the dx product in registers across one more workgroup barrier before adding it
-#endif
-
-#ifndef WM_BWD_ABLATE_FWD_STATE
-#define WM_BWD_ABLATE_FWD_STATE 0 // diagnostics: 1 = core_bwd_reduce_body without the forward recurrence (wrong results; what handing the forward's states over could save)
-#endif
 #ifndef WM_BWD_STAMP
 #define WM_BWD_STAMP 0           // diagnostics: cycle totals per phase of core_bwd_chunk_kernel (tools/core_bwd_stamps.py)
 #endif
@@ -56,9 +46,7 @@ __device__ unsigned long long g_bwd_stamps[2 * 2 * 11];
 // rows 12..15 of every 16-channel tile, run-to-run different, only in the kernel instantiation whose schedule puts the
 // adds right behind the chain); 16 more wait states tied to the register cost nothing measurable.
 __device__ __forceinline__ void mfma_settle(core_f4& acc) {
-#if WM_BWD_MFMA_NOP
     asm volatile("s_nop 15\n\ts_nop 0" : "+v"(acc));
-#endif
 }
 
 __device__ __forceinline__ float add_f32_plain(float a, float b) {
@@ -66,6 +54,18 @@ __device__ __forceinline__ float add_f32_plain(float a, float b) {
     asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+
+constexpr int kPartPadFused = 8;   // partial record (CoreBwdArgs::part): NP (dA) + [dD, dbias, dWdt[0..3], 0, 0]
+
+// tile of chunk t0 covers positions plo .. plo + 15; LDS column tt is scan time t0 + tt: position plo + tt forward,
+// plo + 15 - tt reversed.  Valid position columns are [c_lo, c_hi).
+template <bool REV> struct FusedTile {
+    long long plo; int c_lo, c_hi;
+    __device__ __forceinline__ FusedTile(long long L, int t0, int tl) {
+        plo = REV ? (L - kBT - t0) : (long long)t0;
+        c_lo = REV ? kBT - tl : 0; c_hi = REV ? kBT : tl;
+    }
+};
 
 struct CoreBwdArgs {
     const float* x;          // (B, D, L) planes of this layout (the map, or its transposed copy)
@@ -301,10 +301,10 @@ __device__ __forceinline__ void core_bwd_reduce_body(const CoreBwdArgs& p, float
                             const float4 bv = *reinterpret_cast<const float4*>(&s_B[tt * NP + 4 * r]);
                             const float4 cv = *reinterpret_cast<const float4*>(&s_C[tt * NP + 4 * r]);
                             const v2f a0 = exp2_2(dt2 * A2[2 * r]), a1 = exp2_2(dt2 * A2[2 * r + 1]);
-#if !WM_BWD_ABLATE_FWD_STATE      // timing-only ablation (profiles/r06/core_bwd_summary_pass_ablation.txt): the summary pass without its forward-state half
+                            // (what the summary pass would cost without this forward-state half was measured with a timing-only
+                            // ablation: profiles/r06/core_bwd_summary_pass_ablation.txt)
                             h[2 * r] = a0 * h[2 * r] + du2 * (v2f){bv.x, bv.y};
                             h[2 * r + 1] = a1 * h[2 * r + 1] + du2 * (v2f){bv.z, bv.w};
-#endif
                             pf[2 * r] *= a0; pf[2 * r + 1] *= a1;
                             gl[2 * r] = pf[2 * r] * (dy2 * (v2f){cv.x, cv.y}) + gl[2 * r];
                             gl[2 * r + 1] = pf[2 * r + 1] * (dy2 * (v2f){cv.z, cv.w}) + gl[2 * r + 1];
@@ -652,10 +652,8 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
         __syncthreads();
         BWD_STAMP(7);                                    // closing + barrier
         // ---- dx tile (in s_dy) += Wx^T [dB | dC] on the matrix cores; D layout: lane (c16 = step, g4) holds channels
-        // 16 t + 4 g4 .. + 3 - every element of the tile has exactly one owner (the dt_r part of dx is added by the store)
-#if WM_BWD_DX_LATE
-        core_f4 dlate[(4 + NW - 1) / NW];
-#endif
+        // 16 t + 4 g4 .. + 3 - every element of the tile has exactly one owner (the dt_r part of dx is added by the store).
+        // (Holding the product in registers across one more workgroup barrier before adding it was tried; no measurement was filed.)
         {
             const int g4 = lane >> 4, c16 = lane & 15;
             core_bf8 gh[KS], gl[KS];
@@ -686,29 +684,11 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, gh[s], acc, 0, 0, 0);
                     }
                     mfma_settle(acc);
-#if WM_BWD_DX_LATE
-                    dlate[i] = acc;
-#else
 #pragma unroll
                     for (int r = 0; r < 4; ++r) s_dy[(16 * t + 4 * g4 + r) * kBRow + c16] += acc[r];
-#endif
                 }
             }
         }
-#if WM_BWD_DX_LATE
-        __syncthreads();
-        {
-            const int g4 = lane >> 4, c16 = lane & 15;
-#pragma unroll
-            for (int i = 0; i < (4 + NW - 1) / NW; ++i) {
-                const int t = w + NW * i;
-                if (t < 4) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s_dy[(16 * t + 4 * g4 + r) * kBRow + c16] += dlate[i][r];
-                }
-            }
-        }
-#endif
         // ---- dWx += g x^T: row tile rt of [d dt_r | dB.. | dC..] x channel tile ct, K = the 16 steps (lanes kq >= 2: zeros).
         // Wave w owns the channel tiles ct = w, w + NW, .. and every row tile: each operand is split once.
         {
