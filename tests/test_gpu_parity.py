@@ -1122,7 +1122,7 @@ def test_bf16_storage_mode_block_and_network(golden):
 # ------------------------------------------------------------------------------------------------
 # HFE-branch helpers ("next" row): floating-point kernels of standard ops -> torch fp32
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C,H,W", [(32, 33, 47), (16, 8, 8), (8, 5, 130)])
+@pytest.mark.parametrize("C,H,W", [(32, 33, 47), (16, 8, 8), (8, 5, 130), (64, 33, 47)])
 def test_layernorm2d_vs_torch(C, H, W):
     ln = arch.LayerNorm2d(C)
     with torch.no_grad():

@@ -45,9 +45,18 @@ class _OpsBackend:
     impl = _hip_ops
 
 
+def _op(name):
+    """The installed backend's operator `name`, or None: a backend without it (the CPU oracle has the drop-in operators only, a
+    test may install an empty object) sends the call site to its PyTorch path.  Every site below asks in this order: the
+    operator (`_op`), then its `<name>_supported` predicate on the same backend - device, dtype and shape limits are stated
+    there, next to the call that enforces them, never here - then `_needs_grad`."""
+    return getattr(_OpsBackend.impl, name, None)
+
+
 def _needs_grad(module, *tensors):
     """Autograd will want gradients through this module: grad mode is on and an input or ANY parameter of the module
-    requires grad (a block with a frozen skip_scale or frozen early layers still has trainable weights inside)."""
+    requires grad (a block with a frozen skip_scale or frozen early layers still has trainable weights inside).  The one
+    place that asks about grad mode; `module` None: the tensors alone."""
     if not torch.is_grad_enabled():
         return False
     if any(t is not None and t.requires_grad for t in tensors):
@@ -59,7 +68,7 @@ def _dwconv(conv, x, act="none"):
     """Depth-wise 3x3 nn.Conv2d (+ optional SiLU / exact GELU).  Inference on the HIP backend goes to the
     streaming HIP kernel; training (autograd) and the test backends use the PyTorch conv."""
     ops = _OpsBackend.impl
-    if hasattr(ops, "dwconv3x3") and x.is_cuda and x.dtype == torch.float32:
+    if _op("dwconv3x3") and ops.dwconv3x3_supported(x):
         if not _needs_grad(conv, x):
             return ops.dwconv3x3(x, conv.weight, conv.bias, act)
         y = ops.dwconv3x3_train(x, conv.weight, conv.bias)          # HIP forward + backward (autograd)
@@ -72,7 +81,7 @@ def _ln_tok(norm, x):
     """nn.LayerNorm over the last axis of token tensors: the HIP kernel pair (forward + backward) on the HIP backend,
     the module elsewhere."""
     ops = _OpsBackend.impl
-    if (hasattr(ops, "layernorm_tok") and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine
+    if (_op("layernorm_tok") and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine
             and norm.bias is not None and len(norm.normalized_shape) == 1
             and ops.layernorm_tok_supported(x, norm.normalized_shape[0])):
         return ops.layernorm_tok(x, norm.weight, norm.bias, norm.eps)
@@ -83,7 +92,7 @@ def _linear(lin, x):
     """Bias-free nn.Linear on token tensors: in training on the HIP backend the weight gradient (a tiny matrix reduced
     over ~5e5 tokens) runs on the MFMA reduction kernel instead of a 32 x 32-tile library GEMM."""
     ops = _OpsBackend.impl
-    if (lin.bias is None and hasattr(ops, "linear_nobias") and torch.is_grad_enabled() and lin.weight.requires_grad
+    if (lin.bias is None and _op("linear_nobias") and _needs_grad(lin)
             and ops.linear_nobias_supported(x, lin.weight)):
         return ops.linear_nobias(x, lin.weight)
     return lin(x)
@@ -95,17 +104,16 @@ def _conv(conv, x, x2=None, x2_index=None, gate=None, residual=None):
     HIP backend is one matrix-core kernel (no concatenation, gather, bias, gate or residual kernels); training
     (autograd) and the test backends compose the PyTorch ops."""
     ops = _OpsBackend.impl
-    if (hasattr(ops, "conv2d") and ops.conv2d_supported(x, conv.weight, x2)
-            and not _needs_grad(conv, x, x2, gate, residual)):
+    train = _needs_grad(conv, x, x2, gate, residual)
+    if _op("conv2d") and ops.conv2d_supported(x, conv.weight, x2) and not train:
         return ops.conv2d(x, conv.weight, conv.bias, x2, x2_index, gate, residual)
     x = _cat_gathered(x, x2, x2_index)
-    if hasattr(ops, "conv2d_train") and ops.conv2d_supported(x, conv.weight) and torch.is_grad_enabled():
+    if train and _op("conv2d_train") and ops.conv2d_supported(x, conv.weight):
         y = ops.conv2d_train(x, conv.weight, conv.bias)             # ops.set_train_conv_mode(): fp16-split HIP kernels by default
     else:
         y = conv(x)
     if gate is not None:
-        if (hasattr(ops, "gate_act") and torch.is_grad_enabled() and y.is_cuda and y.dtype == torch.float32
-                and ops.gate_supported(gate, y)):
+        if train and _op("gate_act") and ops.gate_supported(gate, y):
             y = ops.gate_act(gate, y, "sigmoid")                    # one launch forward, one backward (training)
         else:
             y = y * torch.sigmoid(gate)
@@ -119,7 +127,7 @@ def _ps_conv(ps, img):
     on the HIP backend: one r x r / stride-r kernel reading the image itself (no unshuffled copy); otherwise the two modules."""
     ops = _OpsBackend.impl
     r, conv = ps[0].downscale_factor, ps[1]
-    if (hasattr(ops, "patchify_conv") and ops.patchify_conv_supported(img, conv.weight, r) and not _needs_grad(conv, img)):
+    if _op("patchify_conv") and ops.patchify_conv_supported(img, conv.weight, r) and not _needs_grad(conv, img):
         return ops.patchify_conv(img, conv.weight, conv.bias, r)
     return _conv(conv, ps[0](img))
 
@@ -131,7 +139,7 @@ def _ln_conv(norm, conv, x):
     if norm is None:
         return _conv(conv, x)
     ops = _OpsBackend.impl
-    if (hasattr(ops, "conv2d_ln") and ops.conv2d_ln_supported(x, conv.weight) and not _needs_grad(conv, x)
+    if (_op("conv2d_ln") and ops.conv2d_ln_supported(x, conv.weight) and not _needs_grad(conv, x)
             and not _needs_grad(norm, x)):
         return ops.conv2d_ln(x, norm.weight, norm.bias, norm.eps, conv.weight, conv.bias)
     return _conv(conv, norm(x))
@@ -178,7 +186,7 @@ class ffn(nn.Module):
     def forward(self, x):
         t = _dwconv(self.conv2, _conv(self.conv1, x))
         ops = _OpsBackend.impl
-        if torch.is_grad_enabled() and t.requires_grad and t.is_cuda and t.dtype == torch.float32 and hasattr(ops, "glu_gate"):
+        if _needs_grad(None, t) and _op("glu_gate") and ops.glu_gate_supported(t):
             return _conv(self.conv3, ops.glu_gate(t, "gelu"))          # training: chunk + gate, one launch each way
         gate, value = t.chunk(2, dim=1)
         return _conv(self.conv3, F.gelu(gate) * value)
@@ -267,12 +275,13 @@ class SS2D(nn.Module):
         return D
 
     # ---- forward ----------------------------------------------------------------------------
-    def forward_core(self, x):
-        """x (B, D_in, H, W) -> four (B, D_in, L) tensors in row-major l (reference :446-478)."""
+    def forward_core(self, x, merged=False):
+        """x (B, D_in, H, W) -> four (B, D_in, L) tensors in row-major l (reference :446-478); merged=True: their sum
+        y1 + y2 + y3 + y4 (:490), which the fused core accumulates inside its kernels."""
         ops = _OpsBackend.impl
         if self._fused_ok(x):
             return ops.ss2d_core(x, self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias,
-                                 self.A_logs, self.Ds)
+                                 self.A_logs, self.Ds, merged=merged)
         B, D, H, W = x.shape
         L, K, N, R = H * W, 4, self.d_state, self.dt_rank
         row = x.reshape(B, D, L)
@@ -291,14 +300,15 @@ class SS2D(nn.Module):
         back = out[:, 2:4].flip(-1)
         y_col = out[:, 1].reshape(B, D, W, H).transpose(2, 3).reshape(B, D, L)
         y_col_back = back[:, 1].reshape(B, D, W, H).transpose(2, 3).reshape(B, D, L)
-        return out[:, 0], back[:, 0], y_col, y_col_back
+        ys = (out[:, 0], back[:, 0], y_col, y_col_back)
+        return ys[0] + ys[1] + ys[2] + ys[3] if merged else ys
 
     def _fused_ok(self, x):
         """The fused HIP core (forward wm_ss2d_core_fwd, backward wm_ss2d_core_bwd) serves inference and training
         on the HIP backend; out-of-range shapes and the test backends take the direction glue +
         selective_scan_fn path below."""
         ops = _OpsBackend.impl
-        if not (hasattr(ops, "ss2d_core") and x.is_cuda and x.dtype == torch.float32):
+        if not (_op("ss2d_core") and x.is_cuda and x.dtype == torch.float32):
             return False
         if not ops.ss2d_core_supported(self.d_inner, self.d_state, self.dt_rank, x.shape[-1], x.shape[-2]):
             return False
@@ -308,17 +318,19 @@ class SS2D(nn.Module):
         B, H, W, C = x.shape
         x, z = _linear(self.in_proj, x).chunk(2, dim=-1)
         x = _dwconv(self.conv2d, x.permute(0, 3, 1, 2).contiguous(), act="silu")
-        if self._fused_ok(x):                      # y1 + y2 + y3 + y4 accumulated inside the kernels
-            y = _OpsBackend.impl.ss2d_core(x, self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias,
-                                           self.A_logs, self.Ds, merged=True)
-        else:
-            y1, y2, y3, y4 = self.forward_core(x)
-            assert y1.dtype == torch.float32
-            y = y1 + y2 + y3 + y4
+        y = self.forward_core(x, merged=True)
         y = y.transpose(1, 2).contiguous().view(B, H, W, -1)
         y = _ln_tok(self.out_norm, y) * F.silu(z)
         y = _linear(self.out_proj, y)
         return self.dropout(y) if self.dropout is not None else y
+
+
+def _scaled_skip(x, scale, o):
+    """x * scale[c] + o on NCHW maps (LFSSBlock's scaled skips, reference :525-526)."""
+    ops = _OpsBackend.impl
+    if _op("scale_add") and ops.scale_add_supported(x, scale, o):
+        return ops.scale_add(x, scale, o)
+    return x * scale.view(1, -1, 1, 1) + o
 
 
 class LFSSBlock(nn.Module):
@@ -338,35 +350,33 @@ class LFSSBlock(nn.Module):
         self.ln_2 = nn.LayerNorm(hidden_dim)
         self.skip_scale2 = nn.Parameter(torch.ones(hidden_dim))
 
-    def _fused_ok(self, x, width=None, height=None):
-        """Whole-block HIP path: inference on the HIP backend for the kernel's shape range (`width`, `height` of the map)."""
-        ops = _OpsBackend.impl
+    def _hip_block_ok(self, x, width=None, height=None):
+        """What both HIP forms of the block need (asked once their operators are known to be there): an fp32 CUDA input, the
+        reference's plain SS2D (no dropout, bias-free projections) and the block kernels' shape range."""
         ss = self.self_attention
-        if not (hasattr(ops, "lfss_block_forward") and x.is_cuda and x.dtype == torch.float32):
-            return False
-        if _needs_grad(self, x):
+        if not (x.is_cuda and x.dtype == torch.float32):
             return False
         if ss.dropout is not None or ss.in_proj.bias is not None or ss.out_proj.bias is not None:
             return False
-        return ops.lfss_block_supported(ss.d_model, ss.d_inner, ss.d_state, ss.dt_rank,
-                                        self.conv_blk.conv1.out_channels, width, height)
+        return _OpsBackend.impl.lfss_block_supported(ss.d_model, ss.d_inner, ss.d_state, ss.dt_rank,
+                                                     self.conv_blk.conv1.out_channels, width, height)
+
+    def _fused_ok(self, x, width=None, height=None):
+        """Whole-block HIP path: inference on the HIP backend for the kernel's shape range (`width`, `height` of the map)."""
+        return bool(_op("lfss_block_forward")) and not _needs_grad(self, x) and self._hip_block_ok(x, width, height)
 
     def _nchw_train_ok(self, x):
         """Training on the HIP backend: the block on NCHW planes, every operator but the gates / skips an autograd
         Function over HIP kernels (LayerNorm2d, 1x1 convolutions, depth-wise conv, the SS2D core) - no token <-> map
         permutes.  Same shape range as the fused inference path."""
-        ops = _OpsBackend.impl
         ss = self.self_attention
-        if not (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+        if not (x.dim() == 4 and _needs_grad(self, x)):
             return False
-        if not all(hasattr(ops, n) for n in ("layernorm2d_train", "conv2d_train", "dwconv3x3_train", "ss2d_core")):
-            return False
-        if ss.dropout is not None or ss.in_proj.bias is not None or ss.out_proj.bias is not None:
+        if not all(_op(n) for n in ("layernorm2d_train", "conv2d_train", "dwconv3x3_train", "ss2d_core")):
             return False
         if not (isinstance(self.ln_1, nn.LayerNorm) and isinstance(self.ln_2, nn.LayerNorm)):
             return False
-        return (ops.lfss_block_supported(ss.d_model, ss.d_inner, ss.d_state, ss.dt_rank, self.conv_blk.conv1.out_channels)
-                and ops.ss2d_core_bwd_supported(ss.d_inner, ss.d_state, ss.dt_rank))
+        return self._hip_block_ok(x) and _OpsBackend.impl.ss2d_core_bwd_supported(ss.d_inner, ss.d_state, ss.dt_rank)
 
     def forward_nchw_train(self, x):
         """(B, C, H, W) -> (B, C, H, W); the same arithmetic as forward() on the (B, HW, C) view (:520-528)."""
@@ -380,16 +390,12 @@ class LFSSBlock(nn.Module):
         xs = F.silu(ops.dwconv3x3_train(xs, ss.conv2d.weight, ss.conv2d.bias))
         y = ops.ss2d_core(xs, ss.x_proj_weight, ss.dt_projs_weight, ss.dt_projs_bias, ss.A_logs, ss.Ds, merged=True)
         y = ops.layernorm2d_train(y.view_as(xs), ss.out_norm.weight, ss.out_norm.bias, ss.out_norm.eps)
-        fused = hasattr(ops, "gate_act") and hasattr(ops, "scale_add")           # gates / skips: one HIP launch each way
-        gated = ops.gate_act(z, y, "silu") if fused and ops.gate_supported(z, y) else y * F.silu(z)
+        # the gate and the scaled skips: one HIP launch each way where the backend has them
+        gated = ops.gate_act(z, y, "silu") if _op("gate_act") and ops.gate_supported(z, y) else y * F.silu(z)
         o = ops.conv2d_train(gated, ss.out_proj.weight.view(C, D, 1, 1))
-        if not fused:
-            t = x * self.skip_scale.view(1, -1, 1, 1) + o
-            u = ops.layernorm2d_train(t, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
-            return t * self.skip_scale2.view(1, -1, 1, 1) + self.conv_blk(u)
-        t = ops.scale_add(x, self.skip_scale, o)
+        t = _scaled_skip(x, self.skip_scale, o)
         u = ops.layernorm2d_train(t, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
-        return ops.scale_add(t, self.skip_scale2, self.conv_blk(u))
+        return _scaled_skip(t, self.skip_scale2, self.conv_blk(u))
 
     def forward(self, input, x_size):
         B, L, C = input.shape
@@ -416,7 +422,7 @@ class LayerNorm2d(nn.Module):
 
     def forward(self, x):
         ops = _OpsBackend.impl
-        if hasattr(ops, "layernorm2d") and x.is_cuda and x.dtype == torch.float32 and x.shape[1] in (8, 16, 32):
+        if _op("layernorm2d") and ops.layernorm2d_supported(x):
             if not _needs_grad(self, x):
                 return ops.layernorm2d(x, self.weight, self.bias, self.eps)
             return ops.layernorm2d_train(x, self.weight, self.bias, self.eps)
@@ -426,25 +432,16 @@ class LayerNorm2d(nn.Module):
         return self.weight.view(1, -1, 1, 1) * y + self.bias.view(1, -1, 1, 1)
 
 
-def _gram_ok(a, b, differentiable=True):
-    """The HIP Gram kernel serves (a, b); `differentiable=False`: the caller takes nothing differentiable from it (the
-    channel matching keeps indices only), so tensors under autograd qualify too."""
-    ops = _OpsBackend.impl
-    return (hasattr(ops, "gram") and a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32
-            and a.shape == b.shape and a.shape[1] <= 32
-            and not (differentiable and torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)))
-
-
 def nearest_candidate_index(maps, candidates, num_matches):
     """Channel matching (reference :618-666): for every channel of `maps` (B, C, HW) the index of its L2-nearest
     channel of `candidates`; keeps the `num_matches` channels whose nearest distance is smallest (original
     channel order).  -> (B, num_matches) int64 channel indices into `candidates`."""
     ops = _OpsBackend.impl
-    if _gram_ok(maps, candidates, differentiable=False):
+    if _op("gram") and ops.gram_supported(maps, candidates):
         # d^2 = |x|^2 + |y|^2 - 2 x.y, the same expansion torch.cdist uses for C > 25 (mm mode).  Indices only leave this
         # function (topk indices are not differentiable in the reference either): training takes the same kernel
         G, nx, ny = ops.gram(maps.detach(), candidates.detach())
-        if hasattr(ops, "match_index") and (num_matches is None or num_matches == -1 or num_matches >= maps.size(1)):
+        if _op("match_index") and ops.match_index_supported(maps.size(1), num_matches):
             return ops.match_index(G, nx, ny)                       # every channel kept: one argmin kernel
         dist = (nx.unsqueeze(2) + ny.unsqueeze(1) - 2.0 * G).clamp_min(1e-30).sqrt()
     else:
@@ -490,10 +487,8 @@ class PAConv(nn.Module):
 
     def forward(self, x, x2=None, x2_index=None):
         ops = _OpsBackend.impl
-        if (hasattr(ops, "conv2d_gated") and self.k3.bias is None and tuple(self.k3.weight.shape[2:]) == (3, 3)
-                and ops.conv2d_supported(x, self.k3.weight, x2)
-                and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
-                                                         for t in (x, x2, self.k3.weight, self.k2.weight)))):
+        if (_op("conv2d_gated") and self.k3.bias is None and tuple(self.k3.weight.shape[2:]) == (3, 3)
+                and ops.conv2d_supported(x, self.k3.weight, x2) and not _needs_grad(self, x, x2)):
             # k3(x) * sigmoid(k2(x)): the 1x1 rides on the 3x3's centre tap, the gate never exists as a tensor
             return _conv(self.k4, ops.conv2d_gated(x, self.k3.weight, self.k2.weight, self.k2.bias, x2, x2_index))
         xin = _cat_gathered(x, x2, x2_index)            # once for both convolutions (and one scatter in the backward)
@@ -578,13 +573,14 @@ class CMTAttention(nn.Module):
         k = k.reshape(b * heads, c // heads, h * w)
         v = v.reshape(b, heads, c // heads, h * w)
         ops = _OpsBackend.impl
-        train_gram = (hasattr(ops, "gram_train") and _gram_ok(q, k, differentiable=False)
-                      and torch.is_grad_enabled() and (q.requires_grad or k.requires_grad))
-        if train_gram or _gram_ok(q, k):
+        train_gram = _needs_grad(None, q, k)               # the Gram matrix under autograd: gram_train, where the backend has it
+        if _op("gram") and ops.gram_supported(q, k) and (not train_gram or _op("gram_train")):
             # normalize(q) @ normalize(k)^T == (q @ k^T) / (max(|q|, eps) max(|k|, eps)): one pass over q, k
             G, nq, nk = ops.gram_train(q, k) if train_gram else ops.gram(q.contiguous(), k.contiguous())
-            if (hasattr(ops, "attn_fold") and c <= 64 and ops.conv2d_supported(x, self.project_out.weight)
-                    and not (torch.is_grad_enabled() and any(t.requires_grad for t in self.parameters()))):
+            # (the fold is forward-only and asks about the module's PARAMETERS alone, as it always has: with every parameter
+            # frozen it is taken for q, k, v under autograd too, and no gradient reaches them through this attention)
+            if (_op("attn_fold") and ops.attn_fold_supported(x, self.project_out.weight, heads)
+                    and not _needs_grad(self)):
                 # project_out(softmax(...) @ v) = (W_po @ blockdiag(attn)) @ v: a tiny kernel folds the (c/heads)^2
                 # attention into the 1x1 weight, the 1x1 convolution kernel applies it (+ bias, + residual)
                 wf = ops.attn_fold(G, nq, nk, self.temperature.reshape(heads), self.project_out.weight, b, heads)
@@ -650,11 +646,8 @@ class SKFF(nn.Module):
     def forward(self, inp_feats):
         b, c = inp_feats[0].shape[:2]
         ops = _OpsBackend.impl
-        x0 = inp_feats[0]
-        if (hasattr(ops, "skff") and self.height == 3 and len(inp_feats) == 3 and x0.is_cuda and x0.dtype == torch.float32
-                and c <= 64 and self.conv_du[0].weight.shape[0] <= 16 and self.conv_du[1].weight.numel() == 1
-                and not (torch.is_grad_enabled() and (any(t.requires_grad for t in inp_feats)
-                                                      or any(p.requires_grad for p in self.parameters())))):
+        if (_op("skff") and self.height == 3 and ops.skff_supported(inp_feats, self.conv_du[0].weight, self.conv_du[1].weight)
+                and not _needs_grad(self, *inp_feats)):
             w_fc = torch.stack([fc.weight.reshape(c, -1) for fc in self.fcs], 0)      # (3, C, d)
             return ops.skff(inp_feats[0], inp_feats[1], inp_feats[2], self.conv_du[0].weight, self.conv_du[1].weight, w_fc)
         stack = torch.stack(list(inp_feats), dim=1)                    # (B, height, C, H, W)
@@ -824,8 +817,8 @@ class UNet(nn.Module):
         sides = (_side_streams(x, 3) if self.two_streams and not _needs_grad(self, x) else (None, None, None))
         pss = (self.ps_down1, self.ps_down2, self.ps_down3)
         ops = _OpsBackend.impl
-        fused_ps = all(hasattr(ops, "patchify_conv") and ops.patchify_conv_supported(img, ps[1].weight, ps[0].downscale_factor)
-                       for ps in pss)
+        fused_ps = _op("patchify_conv") and all(ops.patchify_conv_supported(img, ps[1].weight, ps[0].downscale_factor)
+                                                for ps in pss)
         if sides[0] is None or fused_ps:
             # (the fused patch embeddings are 0.18 ms per UHD image together: issued on the main stream)
             d, d_ready = [_ps_conv(ps, img) for ps in pss], (None, None, None)

@@ -621,11 +621,16 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
 # ------------------------------------------------------------------------------------------------
 # LayerNorm2d (HFE branch, forward only)
 # ------------------------------------------------------------------------------------------------
+def layernorm2d_supported(x):
+    """Maps wm_layernorm2d_fwd / _bwd cover (layernorm2d, layernorm2d_train): fp32 NCHW, C in {8, 16, 32, 64}."""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] in (8, 16, 32, 64)
+
+
 def layernorm2d(x, weight, bias, eps):
     """Per-pixel LayerNorm over channels of an NCHW fp32 map (reference LayerNorm2d, :532-569)."""
     _require_cuda("layernorm2d", x, weight, bias)
     B, C, H, W = x.shape
-    if C not in (8, 16, 32, 64) or x.dtype != torch.float32:
+    if not layernorm2d_supported(x):
         raise NotImplementedError("layernorm2d: fp32, C in {8, 16, 32, 64}")
     x = x.contiguous()
     y = torch.empty_like(x)
@@ -636,12 +641,18 @@ def layernorm2d(x, weight, bias, eps):
 # ------------------------------------------------------------------------------------------------
 # channel Gram matrix over pixels (HFE branch, forward only)
 # ------------------------------------------------------------------------------------------------
+def gram_supported(x, y):
+    """Pairs wm_gram_fwd covers (gram, gram_train): two fp32 (B, C <= 32, L) tensors of equal shape."""
+    return (x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and x.shape == y.shape
+            and x.shape[1] <= 32)
+
+
 def gram(x, y):
     """x, y (B, C, L) fp32, C <= 32 -> (G (B, C, C) = x @ y^T over L, |x_i|^2 (B, C), |y_j|^2 (B, C))."""
     lib = _lib.load()
     _require_cuda("gram", x, y)
     B, C, L = x.shape
-    if y.shape != x.shape or C > 32 or x.dtype != torch.float32 or y.dtype != torch.float32:
+    if not gram_supported(x, y):
         raise NotImplementedError("gram: two fp32 (B, C<=32, L) tensors of equal shape")
     x, y = x.contiguous(), y.contiguous()
     buf = torch.empty(B * C * (C + 2), dtype=torch.float32, device=x.device)
@@ -851,10 +862,15 @@ class _GluGate(torch.autograd.Function):
         return gt, None
 
 
+def glu_gate_supported(t):
+    """Tensors _GluGate covers: fp32 (B, 2C, H, W) with B <= 65535 (the batch is a grid dimension of wm_gate_fwd / _bwd)."""
+    return t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] % 2 == 0 and t.shape[0] <= 65535
+
+
 def glu_gate(t, act):
     """act(t[:, :C]) * t[:, C:] for a (B, 2C, H, W) fp32 tensor, act in {"silu", "gelu"}, differentiable (_GluGate)."""
     _require_cuda("glu_gate", t)
-    if t.dim() != 4 or t.shape[1] % 2 or t.shape[0] > 65535:
+    if not glu_gate_supported(t):
         raise NotImplementedError("glu_gate: a (B, 2C, H, W) tensor")
     return _GluGate.apply(t, _ACTS[act])
 
@@ -897,10 +913,17 @@ class _ScaleAdd(torch.autograd.Function):
         return gx, gs.view(ctx.scale_shape), g
 
 
+def scale_add_supported(x, scale, o):
+    """Operands _ScaleAdd covers: (B, C, H, W) x and o of one shape, a C-element scale, B C <= 65535 (the planes are a grid
+    dimension of wm_scale_add_fwd / _bwd)."""
+    return (x.is_cuda and x.dim() == 4 and x.shape == o.shape and scale.numel() == x.shape[1]
+            and x.shape[0] * x.shape[1] <= 65535)
+
+
 def scale_add(x, scale, o):
     """x * scale.view(1, C, 1, 1) + o for (B, C, H, W) fp32 tensors and a C-element scale, differentiable."""
     _require_cuda("scale_add", x, scale, o)
-    if x.dim() != 4 or x.shape != o.shape or scale.numel() != x.shape[1] or x.shape[0] * x.shape[1] > 65535:
+    if not scale_add_supported(x, scale, o):
         raise NotImplementedError("scale_add: (B, C, H, W) operands with B C <= 65535 and a C-element scale")
     return _ScaleAdd.apply(x, scale, o)
 
@@ -908,6 +931,12 @@ def scale_add(x, scale, o):
 # ------------------------------------------------------------------------------------------------
 # depth-wise 3x3 convolution (+ bias, + SiLU) - inference path of SS2D.conv2d / ffn.conv2
 # ------------------------------------------------------------------------------------------------
+def dwconv3x3_supported(x):
+    """Maps the module path (a depth-wise nn.Conv2d of the network: dwconv3x3, or dwconv3x3_train under autograd) takes: fp32
+    on the GPU.  dwconv3x3 itself also serves the bf16-storage planes that lfss_block_forward hands it; a module never sees those."""
+    return x.is_cuda and x.dtype == torch.float32
+
+
 def dwconv3x3(x, weight, bias=None, act="none", flip=False):
     """F.conv2d(x, weight, bias, stride=1, padding=1, groups=C) [+ SiLU / exact GELU when act == 'silu' / 'gelu'] for a
     (C, 1, 3, 3) weight, NCHW fp32 (or bf16 planes: fp32 arithmetic, bf16 storage), forward only (no autograd graph is
@@ -1004,6 +1033,11 @@ def y_channel_u8(img, layout="HWC", bgr=True):
     return y if img.dim() == 4 else y[0]
 
 
+def match_index_supported(C, num_matches):
+    """match_index keeps every one of the C channels: `num_matches` must not ask for a selection among them."""
+    return num_matches is None or num_matches == -1 or num_matches >= C
+
+
 def match_index(G, nx, ny):
     """Channel matching with every channel kept: (B, C) int32 index of the L2-nearest candidate channel from the
     Gram outputs of `gram(maps, candidates)` (argmin_j |x_c|^2 + |y_j|^2 - 2 x_c . y_j)."""
@@ -1014,15 +1048,33 @@ def match_index(G, nx, ny):
     return idx
 
 
+def _attn_fold_channels_ok(C, heads):
+    return C <= 64 and C % heads == 0
+
+
+def attn_fold_supported(x, w_po, heads):
+    """The folded attention serves the (B, C, H, W) map `x` (the values) with the 1x1 projection weight `w_po`: wm_attn_fold's
+    C <= 64 channels in `heads` equal groups, and the 1x1 convolution kernel (conv2d) that applies the folded weight."""
+    return _attn_fold_channels_ok(x.shape[1], heads) and conv2d_supported(x, w_po)
+
+
 def attn_fold(G, nq, nk, temperature, w_po, batch, heads):
     """(batch, C, C) = w_po @ blockdiag_h softmax(G / (|q||k|) * temperature): the transposed attention folded into its
     1x1 output projection.  G (batch * heads, ch, ch), nq / nk (batch * heads, ch) squared norms."""
     _require_cuda("attn_fold", G, nq, nk, temperature, w_po)
     C = w_po.shape[0]
+    if not _attn_fold_channels_ok(C, heads):
+        raise NotImplementedError("attn_fold: C <= 64 channels in `heads` equal groups")
     out = torch.empty((batch, C, C), dtype=torch.float32, device=G.device)
     _launch(G.device, "wm_attn_fold", G.contiguous(), nq.contiguous(), nk.contiguous(), temperature.detach().contiguous(),
             w_po.detach().reshape(C, C).contiguous(), out, batch, C, heads)
     return out
+
+
+def skff_supported(feats, w_du, prelu):
+    """Inputs wm_skff_fwd covers: three fp32 (B, C <= 64, H, W) maps, a (d <= 16, C) squeeze weight, a one-element PReLU."""
+    return (len(feats) == 3 and all(t.is_cuda and t.dtype == torch.float32 for t in feats) and feats[0].shape[1] <= 64
+            and w_du.shape[0] <= 16 and prelu.numel() == 1)
 
 
 def skff(x0, x1, x2, w_du, prelu, w_fc):
@@ -1033,6 +1085,8 @@ def skff(x0, x1, x2, w_du, prelu, w_fc):
     d = w_du.shape[0]
     if x1.shape != x0.shape or x2.shape != x0.shape or x0.dtype != torch.float32:
         raise RuntimeError("skff: three fp32 tensors of equal shape")
+    if not skff_supported((x0, x1, x2), w_du, prelu):
+        raise NotImplementedError("skff: C <= 64, d <= 16 and a one-element PReLU")
     x0, x1, x2 = x0.contiguous(), x1.contiguous(), x2.contiguous()
     out = torch.empty_like(x0)
     ws = torch.empty(lib.wm_skff_workspace_bytes(B, C), dtype=torch.uint8, device=x0.device)
