@@ -889,6 +889,52 @@ def test_core_abi_error_codes_from_real_calls():
     torch.cuda.synchronize()
 
 
+def test_lfss_abi_status_codes_at_c32_and_unsupported_widths():
+    """The five LFSS entry points called directly: an empty problem at C = 32 (B = 0, L = 0 / H = 0) is WM_OK - C = 32 has
+    matrix-core kernels only, and an empty call must not fall through to the scalar kernels' width check; ny = 2 is WM_EINVAL;
+    a width without kernels is WM_EUNSUPPORTED (C = 12 everywhere, C = 16 for the recomputing middle kernel)."""
+    from wave_mamba_amd import _lib
+    lib = _lib.load()
+    OK, EINVAL, EUNSUPPORTED = 0, -1, -5
+    C, D, H, W = 32, 64, 2, 32
+    L = H * W
+    t = lambda *s: torch.randn(*s, device=DEV)
+    p = lambda a: a.data_ptr()
+    tok, tok1, out = t(1, L, C), t(1, L, C), t(1, L, C)
+    x, z, f, fc, y4 = t(1, D, L), t(1, D, L), t(1, D, L), t(1, D, L), t(4, 1, D, L)
+    ln1w, ln1b, ln2w, ln2b, onw, onb = t(C), t(C), t(C), t(C), t(D), t(D)
+    Win, Wout, W1, b1, W3, b3, sk1, sk2, cw, cb = t(2 * D, C), t(C, D), t(D, C), t(D), t(C, C), t(C), t(C), t(C), t(D, 3, 3), t(D)
+    st = torch.cuda.current_stream().cuda_stream
+    mid_tail = (p(onw), p(onb), 1e-5, p(Wout), p(sk1), p(ln2w), p(ln2b), 1e-5, p(W1), p(b1), p(tok1), p(f))
+
+    def lfss_in(B=1, L=L, C=C):
+        return lib.wm_lfss_in_fwd(p(tok), 0, p(ln1w), p(ln1b), 1e-5, p(Win), p(x), p(z), B, L, C, 0, st)
+
+    def lfss_mid(B=1, L=L, C=C, ny=4):
+        return lib.wm_lfss_mid_fwd(p(y4), ny, D * L, p(z), p(tok), 0, *mid_tail, B, L, C, 0, st)
+
+    def lfss_mid_rz(B=1, L=L, C=C, ny=4):
+        return lib.wm_lfss_mid_rz_fwd(p(y4), ny, D * L, p(tok), 0, p(ln1w), p(ln1b), 1e-5, p(Win), *mid_tail, B, L, C, 0, st)
+
+    def lfss_out(B=1, L=L, C=C):
+        return lib.wm_lfss_out_fwd(p(fc), p(tok1), p(W3), p(b3), p(sk2), p(out), 0, B, L, C, 0, st)
+
+    def lfss_out_conv(B=1, H=H):
+        return lib.wm_lfss_out_conv_fwd(p(f), p(cw), p(cb), p(tok1), p(W3), p(b3), p(sk2), p(out), 0, B, H, W, C, 0, st)
+
+    for call in (lfss_in, lfss_mid, lfss_mid_rz, lfss_out, lfss_out_conv):
+        assert call() == OK, call.__name__                       # the valid call the others vary
+        assert call(B=0) == OK, call.__name__
+    for call in (lfss_in, lfss_mid, lfss_mid_rz, lfss_out):
+        assert call(L=0) == OK, call.__name__
+    assert lfss_out_conv(H=0) == OK
+    assert lfss_mid(ny=2) == EINVAL and lfss_mid_rz(ny=2) == EINVAL
+    for call in (lfss_in, lfss_mid, lfss_out):
+        assert call(C=12) == EUNSUPPORTED, call.__name__
+    assert lfss_mid_rz(C=16) == EUNSUPPORTED
+    torch.cuda.synchronize()
+
+
 # ------------------------------------------------------------------------------------------------
 # whole LFSSBlock on the HIP path (reference LFSSBlock.forward, :520-528)
 # ------------------------------------------------------------------------------------------------

@@ -30,8 +30,20 @@ constexpr int kDwRows = 16;     // output rows per thread strip (the kernels' `r
 
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }
 
-// exact (erf) GELU, nn.GELU() default: FeedForward.project_out[1] after its depth-wise conv (reference :739-741)
-__device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+// exact (erf) GELU, nn.GELU() default: FeedForward.project_out[1] after its depth-wise conv (reference :739-741) and the gated
+// ffn of LFSSBlock (:227) - the one definition the LFSS kernels use too
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+
+// The depth-wise sum of one output value in its ONE order: bias, then the taps row by row.  w: 9 taps; r0 / r1 / r2: the three
+// input rows' values left, centre, right.  dwconv3x3_kernel and the closing LFSS kernels that fold this convolution in
+// (lfss_mfma.hip.h) all form the sum here, which is what keeps the fused and unfused paths bit-identical.
+__device__ __forceinline__ float dw_taps9(float bias, const float* w, const float* r0, const float* r1, const float* r2) {
+    float acc = bias;
+    acc = fmaf(w[0], r0[0], acc); acc = fmaf(w[1], r0[1], acc); acc = fmaf(w[2], r0[2], acc);
+    acc = fmaf(w[3], r1[0], acc); acc = fmaf(w[4], r1[1], acc); acc = fmaf(w[5], r1[2], acc);
+    acc = fmaf(w[6], r2[0], acc); acc = fmaf(w[7], r2[1], acc); acc = fmaf(w[8], r2[2], acc);
+    return acc;
+}
 
 // TP: storage type of the x / y planes (float, or bf16_t in the bf16-storage mode: fp32 arithmetic either way)
 // LPR: lanes per strip row.  64: a wave is one strip of 256 columns.  32 / 16 (maps of <= 128 / <= 64 columns - the 128 x 128 and
@@ -115,11 +127,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const TP* __restrict__ x
                 float o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float acc = bv;
-                    acc = fmaf(k[0], r0[j], acc); acc = fmaf(k[1], r0[j + 1], acc); acc = fmaf(k[2], r0[j + 2], acc);
-                    acc = fmaf(k[3], r1[j], acc); acc = fmaf(k[4], r1[j + 1], acc); acc = fmaf(k[5], r1[j + 2], acc);
-                    acc = fmaf(k[6], r2[j], acc); acc = fmaf(k[7], r2[j + 1], acc); acc = fmaf(k[8], r2[j + 2], acc);
-                    o[j] = ACT == 1 ? silu_f(acc) : ACT == 2 ? gelu_f(acc) : acc;
+                    const float acc = dw_taps9(bv, k, r0 + j, r1 + j, r2 + j);
+                    o[j] = ACT == 1 ? silu_f(acc) : ACT == 2 ? gelu_erf(acc) : acc;
                 }
                 if (colok) {
                     if constexpr (VEC) {
@@ -159,10 +168,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const TP* __restrict__ x
         }
     }
 }
-
-}  // namespace wm
-
-namespace wm {
 
 // ---- weight / bias gradient of the depth-wise 3x3 convolution ------------------------------------------
 // dW[c][i][j] = sum_{b,h,w} gy[b,c,h,w] * x[b,c,h+i-1,w+j-1]   (zero padding),   db[c] = sum gy[b,c,h,w]

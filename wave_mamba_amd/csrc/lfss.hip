@@ -7,14 +7,60 @@
 
 using namespace wm;
 
-// lanes per strip row of the depth-wise kernels (dwconv.hip.h): narrow maps put 2 / 4 planes side by side in a wave
-static int dw_lanes_per_row(int W, bool vec) { return !vec || W > 128 ? 64 : (W > 64 ? 32 : 16); }
-// rows per strip: 16 (every input row fetched 18 / 16 times), or 8 / 4 on small problems - a strip is a chain of dependent row
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// A runtime channel count as a compile-time one: f(c) with c() == C for C among the widths the caller supports (WIDTHS: their sum, each
+// a power of two); false when C is none of them.  Widths outside WIDTHS are not instantiated.
+template <unsigned WIDTHS, typename F>
+static bool with_channels(int C, F&& f) {
+    if constexpr ((WIDTHS & 64u) != 0) if (C == 64) { f(int_c<64>{}); return true; }
+    if constexpr ((WIDTHS & 32u) != 0) if (C == 32) { f(int_c<32>{}); return true; }
+    if constexpr ((WIDTHS & 16u) != 0) if (C == 16) { f(int_c<16>{}); return true; }
+    if constexpr ((WIDTHS & 8u) != 0) if (C == 8) { f(int_c<8>{}); return true; }
+    return false;
+}
+// One thread per position of (B, L), 256 per workgroup, kernel class `prof_class`: launch(int_c<C>{}, grid, block, stream) for C among
+// WIDTHS.  An empty problem is WM_OK whatever C is.
+template <unsigned WIDTHS, typename F>
+static int launch_per_position(int prof_class, int B, int64_t L, int C, void* stream, F&& launch) {
+    const long long total = (long long)B * L;
+    if (total == 0) return WM_OK;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(prof_class, st);
+    if (!with_channels<WIDTHS>(C, [&](auto c) { launch(c, grid, block, st); })) return WM_EUNSUPPORTED;
+    return launch_status();
+}
+
+// rows per strip of the depth-wise kernels (dwconv.hip.h): 16 (every input row fetched 18 / 16 times), or 8 / 4 on small problems - a strip is a chain of dependent row
 // fetches, and 16-row strips of a 64 x 64 map are 128-384 workgroups for 256 compute units (21 us per weight-gradient launch at
 // BASELINE config 3's level 3, whatever the lanes did)
 static int dw_strip_rows(int H, long long column_blocks, long long plane_groups) {
     const long long waves16 = column_blocks * ((H + kDwRows - 1) / kDwRows) * plane_groups;
     return waves16 >= 2048 ? kDwRows : (waves16 >= 1024 ? 8 : 4);
+}
+
+// Launch geometry of the depth-wise kernels: `vec` (16-byte accesses), lanes per strip row, groups of planes that share a wave, rows
+// per strip (short_strips: dw_strip_rows; otherwise kDwRows)
+struct DwGeometry { bool vec; int lpr, rows; long long pgroups; dim3 grid, block; };
+static DwGeometry dw_geometry(int H, int W, long long planes, bool vec, bool short_strips) {
+    DwGeometry g;
+    g.vec = vec;
+    g.lpr = !vec || W > 128 ? 64 : (W > 64 ? 32 : 16);          // narrow maps put 2 / 4 planes side by side in a wave
+    g.pgroups = (planes + 64 / g.lpr - 1) / (64 / g.lpr);
+    g.block = dim3(64, 4);
+    const long long column_blocks = (W + 4 * g.lpr - 1) / (4 * g.lpr);
+    g.rows = short_strips ? dw_strip_rows(H, column_blocks, g.pgroups) : kDwRows;
+    g.grid = dim3((unsigned)column_blocks, (unsigned)((H + 4 * g.rows - 1) / (4 * g.rows)), (unsigned)(g.pgroups < 65535 ? g.pgroups : 65535));
+    return g;
+}
+// the kernels' <VEC, LPR> for a geometry: f(std::bool_constant<VEC>{}, int_c<LPR>{})
+template <typename F>
+static void with_dw_lanes(const DwGeometry& g, F&& f) {
+    if (!g.vec) f(std::false_type{}, int_c<64>{});
+    else if (g.lpr == 64) f(std::true_type{}, int_c<64>{});
+    else if (g.lpr == 32) f(std::true_type{}, int_c<32>{});
+    else f(std::true_type{}, int_c<16>{});
 }
 
 // Launch geometry of the C = 32 matrix-core kernels (lfss_mfma.hip.h): groups of 64 positions, `gpw` of them per wave, enough
@@ -49,6 +95,20 @@ static int lfss_mid32_launch(const void* ysum, int ny, int64_t ystride, const vo
     return launch_status();
 }
 
+// The argument checks wm_lfss_mid_fwd and wm_lfss_mid_rz_fwd share (have_all: none of the pointers the form reads or writes is null).
+// rz, the recomputing form: C == 32 only, and an empty problem is WM_OK before its pointers are looked at.
+static int lfss_mid_check(bool rz, bool have_all, const float* tok, int tok_nchw, const float* tok1, int ny, int B, int64_t L, int C,
+                          int plane_dtype) {
+    if (B < 0 || L < 0 || (ny != 1 && ny != 4)) return WM_EINVAL;
+    if (rz ? (C != 32 || (plane_dtype != WM_F32 && plane_dtype != WM_BF16))
+           : (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32))) return WM_EUNSUPPORTED;
+    const bool empty = B == 0 || L == 0;
+    if (rz && empty) return WM_OK;
+    if (!empty && !have_all) return WM_ENULL;
+    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    return WM_OK;
+}
+
 extern "C" {
 
 int wm_dwconv3x3_fwd(const void* x, const float* weight, const float* bias, void* y, int B, int C,
@@ -60,42 +120,19 @@ int wm_dwconv3x3_fwd(const void* x, const float* weight, const float* bias, void
     const long long planes = (long long)B * C;
     if (planes == 0 || H == 0 || W == 0) return WM_OK;
     if (!x || !weight || !y) return WM_ENULL;
-    const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(y);      // (bf16: 8-byte accesses, covered by the same test)
-    const int lpr = dw_lanes_per_row(W, vec);
-    const long long pgroups = (planes + 64 / lpr - 1) / (64 / lpr);
-    const dim3 block(64, 4);
-    const int rows = dw_strip_rows(H, (W + 4 * lpr - 1) / (4 * lpr), pgroups);
-    const dim3 grid((unsigned)((W + 4 * lpr - 1) / (4 * lpr)), (unsigned)((H + 4 * rows - 1) / (4 * rows)),
-                    (unsigned)(pgroups < 65535 ? pgroups : 65535));
+    // (vec - bf16: 8-byte accesses, covered by the same alignment test)
+    const DwGeometry g = dw_geometry(H, W, planes, (W % 4 == 0) && aligned16(x) && aligned16(y), true);
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(act == 1 ? 7 : 17, st);       // + SiLU: SS2D's conv2d (:486-487, hot path); the others belong to the HFE branch / the ffn
-#define WM_DW1(ACT, VEC, LPR)                                                                                                 \
-    WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((dwconv3x3_kernel<ACT, VEC, TP, LPR>), grid, block, 0, st, (const TP*)x,   \
-                                                      weight, bias, (TP*)y, C, H, W, planes, rows, flip))
-#define WM_DW(ACT)                                                                                                            \
-    do {                                                                                                                      \
-        if (!vec) WM_DW1(ACT, false, 64); else if (lpr == 64) WM_DW1(ACT, true, 64);                                          \
-        else if (lpr == 32) WM_DW1(ACT, true, 32); else WM_DW1(ACT, true, 16);                                                \
-    } while (0)
-    if (act == 1) WM_DW(1); else if (act == 2) WM_DW(2); else WM_DW(0);
-#undef WM_DW
-#undef WM_DW1
+    auto launch = [&](auto act_c) {
+        with_dw_lanes(g, [&](auto vec, auto lpr) {
+            WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((dwconv3x3_kernel<act_c(), vec(), TP, lpr()>), g.grid, g.block, 0, st, (const TP*)x,
+                                                              weight, bias, (TP*)y, C, H, W, planes, g.rows, flip));
+        });
+    };
+    if (act == 1) launch(int_c<1>{}); else if (act == 2) launch(int_c<2>{}); else launch(int_c<0>{});
     return launch_status();
 }
-
-#define WM_LFSS_DISPATCH(PROFCLASS, KERNEL, ...)                                                   \
-    do {                                                                                           \
-        const long long total = (long long)B * L;                                                  \
-        if (total == 0) return WM_OK;                                                              \
-        const dim3 grid((unsigned)((total + 255) / 256)), block(256);                              \
-        hipStream_t st = (hipStream_t)stream;                                                      \
-        ProfScope ps(PROFCLASS, st);                                                               \
-        if (C == 32) hipLaunchKernelGGL((KERNEL<32>), grid, block, 0, st, __VA_ARGS__);            \
-        else if (C == 16) hipLaunchKernelGGL((KERNEL<16>), grid, block, 0, st, __VA_ARGS__);       \
-        else if (C == 8) hipLaunchKernelGGL((KERNEL<8>), grid, block, 0, st, __VA_ARGS__);         \
-        else return WM_EUNSUPPORTED;                                                               \
-        return launch_status();                                                                    \
-    } while (0)
 
 int wm_lfss_in_fwd(const float* tok, int tok_nchw, const float* ln_w, const float* ln_b, float ln_eps,
                    const float* in_proj_weight, void* x_, void* z_, int B, int64_t L, int C, int plane_dtype, void* stream) {
@@ -113,7 +150,9 @@ int wm_lfss_in_fwd(const float* tok, int tok_nchw, const float* ln_w, const floa
                                                           ln_eps, in_proj_weight, (TP*)x_, (TP*)z_, B, (long long)L, g.ngl, g.ngroups, g.gpw));
         return launch_status();
     }
-    WM_LFSS_DISPATCH(5, lfss_in_kernel, tok, tok_nchw, ln_w, ln_b, ln_eps, in_proj_weight, x, z, B, (long long)L);
+    return launch_per_position<16 | 8>(5, B, L, C, stream, [&](auto c, dim3 grid, dim3 block, hipStream_t st) {
+        hipLaunchKernelGGL((lfss_in_kernel<c()>), grid, block, 0, st, tok, tok_nchw, ln_w, ln_b, ln_eps, in_proj_weight, x, z, B, (long long)L);
+    });
 }
 
 int wm_lfss_mid_fwd(const void* ysum_, int ny, int64_t ystride, const void* z_, const float* tok, int tok_nchw, const float* out_norm_w,
@@ -121,18 +160,19 @@ int wm_lfss_mid_fwd(const void* ysum_, int ny, int64_t ystride, const void* z_, 
                     const float* skip_scale, const float* ln2_w, const float* ln2_b, float ln2_eps,
                     const float* conv1_weight, const float* conv1_bias, float* tok1, void* f_, int B, int64_t L,
                     int C, int plane_dtype, void* stream) {
-    if (B < 0 || L < 0 || (ny != 1 && ny != 4)) return WM_EINVAL;
-    if (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32)) return WM_EUNSUPPORTED;
-    const float* ysum = (const float*)ysum_; const float* z = (const float*)z_; float* f = (float*)f_;
-    if (B && L && (!ysum || !z || !tok || !out_norm_w || !out_norm_b || !out_proj_weight || !skip_scale || !ln2_w ||
-                   !ln2_b || !conv1_weight || !conv1_bias || !tok1 || !f)) return WM_ENULL;
-    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    const bool have_all = ysum_ && z_ && tok && out_norm_w && out_norm_b && out_proj_weight && skip_scale && ln2_w && ln2_b && conv1_weight &&
+                          conv1_bias && tok1 && f_;
+    const int status = lfss_mid_check(false, have_all, tok, tok_nchw, tok1, ny, B, L, C, plane_dtype);
+    if (status != WM_OK) return status;
     if (C == 32 && B && L)                                   // the shipped width: projections on the matrix cores
         return lfss_mid32_launch<false>(ysum_, ny, ystride, z_, tok, tok_nchw, nullptr, nullptr, 0.0f, nullptr, out_norm_w, out_norm_b,
                                         out_norm_eps, out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
                                         tok1, f_, B, L, plane_dtype, (hipStream_t)stream);
-    WM_LFSS_DISPATCH(9, lfss_mid_kernel, ysum, ny, (long long)ystride, z, tok, tok_nchw, out_norm_w, out_norm_b, out_norm_eps, out_proj_weight,
-                     skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias, tok1, f, B, (long long)L);
+    return launch_per_position<16 | 8>(9, B, L, C, stream, [&](auto c, dim3 grid, dim3 block, hipStream_t st) {
+        hipLaunchKernelGGL((lfss_mid_kernel<c()>), grid, block, 0, st, (const float*)ysum_, ny, (long long)ystride, (const float*)z_, tok, tok_nchw,
+                           out_norm_w, out_norm_b, out_norm_eps, out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias, tok1,
+                           (float*)f_, B, (long long)L);
+    });
 }
 
 // wm_lfss_mid_fwd with the gate z RECOMPUTED from `tok` (ln_1 + in_proj rows [D, 2D) on the matrix cores, bit-identical to
@@ -143,12 +183,10 @@ int wm_lfss_mid_rz_fwd(const void* ysum_, int ny, int64_t ystride, const float* 
                        const float* skip_scale, const float* ln2_w, const float* ln2_b, float ln2_eps,
                        const float* conv1_weight, const float* conv1_bias, float* tok1, void* f_, int B, int64_t L,
                        int C, int plane_dtype, void* stream) {
-    if (B < 0 || L < 0 || (ny != 1 && ny != 4)) return WM_EINVAL;
-    if (C != 32 || (plane_dtype != WM_F32 && plane_dtype != WM_BF16)) return WM_EUNSUPPORTED;
-    if (B == 0 || L == 0) return WM_OK;
-    if (!ysum_ || !tok || !ln1_w || !ln1_b || !in_proj_weight || !out_norm_w || !out_norm_b || !out_proj_weight || !skip_scale ||
-        !ln2_w || !ln2_b || !conv1_weight || !conv1_bias || !tok1 || !f_) return WM_ENULL;
-    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    const bool have_all = ysum_ && tok && ln1_w && ln1_b && in_proj_weight && out_norm_w && out_norm_b && out_proj_weight && skip_scale &&
+                          ln2_w && ln2_b && conv1_weight && conv1_bias && tok1 && f_;
+    const int status = lfss_mid_check(true, have_all, tok, tok_nchw, tok1, ny, B, L, C, plane_dtype);
+    if (status != WM_OK || B == 0 || L == 0) return status;
     return lfss_mid32_launch<true>(ysum_, ny, ystride, nullptr, tok, tok_nchw, ln1_w, ln1_b, ln1_eps, in_proj_weight, out_norm_w,
                                    out_norm_b, out_norm_eps, out_proj_weight, skip_scale, ln2_w, ln2_b, ln2_eps, conv1_weight,
                                    conv1_bias, tok1, f_, B, L, plane_dtype, (hipStream_t)stream);
@@ -169,7 +207,9 @@ int wm_lfss_out_fwd(const void* fc_, const float* tok1, const float* conv3_weigh
                                                           conv3_bias, skip_scale2, out, out_nchw, B, (long long)L, g.ngl, g.ngroups, g.gpw));
         return launch_status();
     }
-    WM_LFSS_DISPATCH(11, lfss_out_kernel, fc, tok1, conv3_weight, conv3_bias, skip_scale2, out, out_nchw, B, (long long)L);
+    return launch_per_position<16 | 8>(11, B, L, C, stream, [&](auto c, dim3 grid, dim3 block, hipStream_t st) {
+        hipLaunchKernelGGL((lfss_out_kernel<c()>), grid, block, 0, st, fc, tok1, conv3_weight, conv3_bias, skip_scale2, out, out_nchw, B, (long long)L);
+    });
 }
 
 int wm_lfss_out_conv_fwd(const void* f_, const float* conv2_weight, const float* conv2_bias, const float* tok1,
@@ -183,6 +223,8 @@ int wm_lfss_out_conv_fwd(const void* f_, const float* conv2_weight, const float*
     if (L > 0x1fffffffLL) return WM_EUNSUPPORTED;                // 32-bit byte offsets inside one channel plane
     if (!f_ || !conv2_weight || !tok1 || !conv3_weight || !conv3_bias || !skip_scale2 || !out) return WM_ENULL;
     if (!aligned16(tok1) || (!out_nchw && !aligned16(out))) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(11, st);
     // accumulating row-window form (round 6, lfss_out_conv_acc_kernel<4>: four output rows of a 64-column strip per wave pass, the
     // closing product accumulated in registers over groups of eight gated channels, one coalesced load per tap row + lane shifts):
     // W % 64 == 0 and >= 2^18 positions.  Measured (profiles/r06/lfss_out_conv_forms.txt, ms per call at UHD levels 1 / 2): banded
@@ -197,18 +239,14 @@ int wm_lfss_out_conv_fwd(const void* f_, const float* conv2_weight, const float*
         if (bpw > 8) bpw = 8;
         const int nchunks = (nbands + bpw - 1) / bpw;
         const long long nwalks = (long long)B * nchunks * nstrips;
-        hipStream_t st3 = (hipStream_t)stream;
-        ProfScope ps3(11, st3);
         WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL((lfss_out_conv_acc_kernel<R, TP>), dim3((unsigned)((nwalks + 3) / 4)), dim3(256), 0,
-                                                          st3, (const TP*)f_, conv2_weight, conv2_bias, tok1, conv3_weight, conv3_bias,
+                                                          st, (const TP*)f_, conv2_weight, conv2_bias, tok1, conv3_weight, conv3_bias,
                                                           skip_scale2, out, out_nchw, B, H, W, nstrips, nbands, bpw, nchunks, nwalks));
         return launch_status();
     }
     // groups per image row for the kernel's banded (column-major) group order (0: linear order, maps whose width is not a multiple of 64)
     const int gpr = (W % 64 == 0) ? W / 64 : 0;
     const Lfss32Grid g = lfss32_grid(B, L, 2048);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(11, st);
     WM_PLANE_DISPATCH(plane_dtype, hipLaunchKernelGGL(lfss_out_conv_mfma_kernel<TP>, g.grid, dim3(256), 0, st, (const TP*)f_, conv2_weight,
                                                       conv2_bias, tok1, conv3_weight, conv3_bias, skip_scale2, out, out_nchw, B, H, W,
                                                       g.ngl, g.ngroups, g.gpw, gpr));
@@ -219,16 +257,10 @@ int wm_layernorm2d_fwd(const float* x, const float* weight, const float* bias, f
                        int64_t L, int C, void* stream) {
     if (B < 0 || L < 0) return WM_EINVAL;
     if (B && L && (!x || !weight || !bias || !y)) return WM_ENULL;
-    if (C == 64) {                                       // SS2D.out_norm on (B, D, L) planes (NCHW training path)
-        const long long total = (long long)B * L;
-        if (total == 0) return WM_OK;
-        hipStream_t st = (hipStream_t)stream;
-        ProfScope ps(16, st);
-        hipLaunchKernelGGL((layernorm2d_kernel<64>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, weight, bias,
-                           eps, y, B, (long long)L);
-        return launch_status();
-    }
-    WM_LFSS_DISPATCH(16, layernorm2d_kernel, x, weight, bias, eps, y, B, (long long)L);
+    // (C == 64: SS2D.out_norm on (B, D, L) planes, NCHW training path)
+    return launch_per_position<64 | 32 | 16 | 8>(16, B, L, C, stream, [&](auto c, dim3 grid, dim3 block, hipStream_t st) {
+        hipLaunchKernelGGL((layernorm2d_kernel<c()>), grid, block, 0, st, x, weight, bias, eps, y, B, (long long)L);
+    });
 }
 
 int wm_dwconv3x3_wgrad(const float* x, const float* gy, float* dW, float* db, int B, int C, int H, int W,
@@ -242,17 +274,11 @@ int wm_dwconv3x3_wgrad(const float* x, const float* gy, float* dW, float* db, in
     const long long planes = (long long)B * C;
     if (planes == 0 || H == 0 || W == 0) return WM_OK;
     if (!x || !gy) return WM_ENULL;
-    const bool vec = (W % 4 == 0) && aligned16(x) && aligned16(gy);
-    const int lpr = dw_lanes_per_row(W, vec);
-    const long long pgroups = (planes + 64 / lpr - 1) / (64 / lpr);
-    const dim3 block(64, 4);
-    const int rows = kDwRows;                  // (shorter strips on small maps: more atomics - twice the time at config 3's level 3)
-    const dim3 grid((unsigned)((W + 4 * lpr - 1) / (4 * lpr)), (unsigned)((H + 4 * rows - 1) / (4 * rows)),
-                    (unsigned)(pgroups < 65535 ? pgroups : 65535));
-    if (!vec) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<false, 64>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
-    else if (lpr == 64) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 64>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
-    else if (lpr == 32) hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 32>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
-    else hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<true, 16>), grid, block, 0, st, x, gy, dW, db, C, H, W, planes, rows);
+    // (kDwRows rows per strip: shorter strips on small maps are more atomics - twice the time at config 3's level 3)
+    const DwGeometry g = dw_geometry(H, W, planes, (W % 4 == 0) && aligned16(x) && aligned16(gy), false);
+    with_dw_lanes(g, [&](auto vec, auto lpr) {
+        hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<vec(), lpr()>), g.grid, g.block, 0, st, x, gy, dW, db, C, H, W, planes, g.rows);
+    });
     return launch_status();
 }
 
@@ -271,10 +297,11 @@ int wm_layernorm2d_bwd(const float* x, const float* weight, const float* gy, flo
     long long blocks = (total * tpp + 255) / 256;
     if (blocks > 512) blocks = 512;                      // grid-stride: few blocks -> few atomics per channel
     const dim3 grid((unsigned)blocks), block(256);
-    if (C == 64) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<64>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
-    else if (C == 32) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<32>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
-    else if (C == 16) hipLaunchKernelGGL((layernorm2d_bwd_kernel<16>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
-    else hipLaunchKernelGGL((layernorm2d_bwd_kernel<8>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
+        constexpr int CC = c();
+        if constexpr (CC >= 32) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<CC>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+        else hipLaunchKernelGGL((layernorm2d_bwd_kernel<CC>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
+    });
     return launch_status();
 }
 
@@ -290,10 +317,10 @@ int wm_layernorm_tok_fwd(const float* x, const float* weight, const float* bias,
     long long blocks = (T + tpb - 1) / tpb;
     if (blocks > 256 * 32) blocks = 256 * 32;
     const dim3 grid((unsigned)blocks), block(256);
-#define WM_LNT(CC) hipLaunchKernelGGL((layernorm_tok_kernel<CC>), grid, block, 0, st, (const float4*)x, (const float4*)weight, \
-                                      (const float4*)bias, eps, (float4*)y, (long long)T)
-    if (C == 64) WM_LNT(64); else if (C == 32) WM_LNT(32); else if (C == 16) WM_LNT(16); else WM_LNT(8);
-#undef WM_LNT
+    with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
+        hipLaunchKernelGGL((layernorm_tok_kernel<c()>), grid, block, 0, st, (const float4*)x, (const float4*)weight, (const float4*)bias, eps,
+                           (float4*)y, (long long)T);
+    });
     return launch_status();
 }
 
@@ -312,10 +339,10 @@ int wm_layernorm_tok_bwd(const float* x, const float* weight, const float* gy, f
     long long blocks = (T + tpb - 1) / tpb;
     if (blocks > 1024) blocks = 1024;                    // grid-stride: few blocks -> few atomics per channel
     const dim3 grid((unsigned)blocks), block(256);
-#define WM_LNTB(CC) hipLaunchKernelGGL((layernorm_tok_bwd_kernel<CC>), grid, block, 0, st, (const float4*)x, (const float4*)weight, \
-                                       (const float4*)gy, eps, (float4*)gx, dweight, dbias, (long long)T)
-    if (C == 64) WM_LNTB(64); else if (C == 32) WM_LNTB(32); else if (C == 16) WM_LNTB(16); else WM_LNTB(8);
-#undef WM_LNTB
+    with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
+        hipLaunchKernelGGL((layernorm_tok_bwd_kernel<c()>), grid, block, 0, st, (const float4*)x, (const float4*)weight, (const float4*)gy, eps,
+                           (float4*)gx, dweight, dbias, (long long)T);
+    });
     return launch_status();
 }
 

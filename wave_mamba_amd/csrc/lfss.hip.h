@@ -16,10 +16,10 @@
 // token rows (C floats) with 16-byte accesses.  Pure streaming: HBM-bound by construction.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "dwconv.hip.h"        // gelu_erf
 
 namespace wm {
 
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 __device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-v)); }
 
 template <int C>
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void lfss_mid_kernel(
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         const float* q = ysum + (b * D + d) * L + p;
-        y[d] = ny == 1 ? q[0] : ny == 2 ? q[0] + q[ystride] : ((q[0] + q[ystride]) + q[2 * ystride]) + q[3 * ystride];     // y1 + y2 + y3 + y4 (:490)
+        y[d] = ny == 1 ? q[0] : ((q[0] + q[ystride]) + q[2 * ystride]) + q[3 * ystride];     // y1 + y2 + y3 + y4 (:490)
     }
     layer_norm<D>(y, on_w, on_b, on_eps);
 #pragma unroll
@@ -187,11 +187,6 @@ __global__ __launch_bounds__(256) void layernorm2d_kernel(const float* __restric
 #pragma unroll
     for (int c = 0; c < C; ++c) y[(bb * C + c) * L + p] = fmaf(w[c], (v[c] - mean) * rstd, b[c]);
 }
-
-
-}  // namespace wm
-
-namespace wm {
 
 // ---- LayerNorm2d backward (reference LayerNormFunction.backward, :545-557) --------------------------------
 //   g = gy * w ;  gx = rstd * (g - yhat * mean_c(g * yhat) - mean_c(g)) ;  dw[c] = sum gy*yhat ;  db[c] = sum gy

@@ -17,9 +17,50 @@
 // 1e-7.  fp32 MFMA keeps fp32 products (no operand splitting).  The kernels are latency-bound rather than HBM-bound
 // (DESIGN.md 4): loads are issued in explicit batches ahead of their use and ahead of the group's stores.
 // Reference: basicsr/archs/wavemamba_arch.py :491-494 (SS2D tail), :525-526 (LFSSBlock), :226-230 (ffn).
+//
+// The five kernels are built from these pieces (each written once, with its layout comment):
+//   group_pos                          group number -> batch image and first position
+//   load_tile32 / store_tile32         a 32-position tile of tokens or planes <-> accumulator layout
+//   tile_normalise, xhalf_sum          LayerNorm statistics over a tile's 16 + 16 registers
+//   acc_quads / acc_rows, skip_add     accumulator registers from an LDS row; tok = tok * skip + acc
+//   aop_slot, acc_chan                 where A operand j of lane l sits in LDS; which channel K-step j carries
+//   stage_aop, stage_aop_blocks, stage_aop_rows, stage_W3, folded_bias, stage_dw_taps     weights into LDS before the group loop
+//   mfma_k4 / mfma_rows                THE K loop: one ds_read_b128 of A operands, then their MFMAs over the tiles.  Every
+//                                      projection runs through it, so lfss_out's K order (acc_chan) is the same in
+//                                      lfss_out_mfma, lfss_out_conv_mfma and lfss_out_conv_acc by construction
+//   store_rows64                       two tiles of a row block -> 256-byte runs of a plane
+//   plane_rsrc, buf_ld, load_dw_taps   one channel plane as a raw buffer; a channel's taps from LDS
+//   dw_taps9 (dwconv.hip.h)            the depth-wise sum in the depth-wise kernel's own order
 #pragma once
 #include <hip/hip_runtime.h>
 #include "haar.hip.h"          // bf16_t, ld1 / st1 (fp32 and bf16 overloads)
+#include "dwconv.hip.h"        // dw_taps9, gelu_erf, dpp_from_lower_lane / dpp_from_upper_lane
+
+// ---- tuning switches (tools/build_variant.sh and tools/bench_lfss_rz.py pass them with -D) --------------------------
+// waves per SIMD the middle kernel is compiled for.  Four (128 registers) spilled 46 vector registers of the ny = 4 fp32
+// form to scratch; three (163 registers, no spills) is 5 % faster on the kernel (6.92 -> 6.60 ms per UHD step for the
+// block glue, tools: build_variant.sh mid3, bench.py twice each, gpurun_out r3z).
+#ifndef WM_LFSS_MID_WAVES
+#define WM_LFSS_MID_WAVES 3
+#endif
+// (the recomputing form - RZ, below - holds the normalised token tile and the gate accumulators beside y: at three waves per SIMD it
+// spills 19 registers; at two - 256 registers, none spilled - it is 3-6 % faster per call, tools/bench_lfss_rz.py with
+// -DWM_LFSS_MID_WAVES=2; the reading form is 25 % slower at two)
+#ifndef WM_LFSS_MID_RZ_WAVES
+#define WM_LFSS_MID_RZ_WAVES 2
+#endif
+#ifndef WM_LFSS_IN_WAVES
+#define WM_LFSS_IN_WAVES 4
+#endif
+// channels per batch of y loads in the recomputing middle kernel (x 4 direction buffers in flight per lane).  It runs two waves per
+// SIMD with registers to spare: 16 channels = 64 loads in flight per lane, 0.71 -> 0.65 ms at UHD level 1 (4.9 TB/s on its
+// 1536 B per position); 32 gains nothing more (tools/bench_lfss_rz.py with -DWM_LFSS_MID_YB_RZ=..)
+#ifndef WM_LFSS_MID_YB_RZ
+#define WM_LFSS_MID_YB_RZ 16
+#endif
+#ifndef WM_LFSS_OUT_TILE
+#define WM_LFSS_OUT_TILE 8        // image rows per band of the column-major group order (0 rows = linear order: pass gpr = 0)
+#endif
 
 namespace wm {
 
@@ -29,6 +70,7 @@ __device__ __forceinline__ float silu_fast(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
 }
 __device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32); }
+__device__ __forceinline__ lfss_v16f mfma32(float a, float b, lfss_v16f acc) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0); }
 
 // waves each take `gpw` consecutive groups of 64 positions; chosen so that the waves fill whole rounds of the
 // `slots` resident waves (1024 SIMDs x the kernel's waves per SIMD), at most 8 groups per wave
@@ -37,6 +79,8 @@ inline int lfss_groups_per_wave(long long ngroups, int slots) {
     long long gpw = (ngroups + rounds * slots - 1) / (rounds * slots);
     return (int)(gpw < 1 ? 1 : gpw);
 }
+// group g of 64 positions -> its batch image b and first position p0 (`ngl` groups per image)
+__device__ __forceinline__ void group_pos(long long g, int ngl, long long& b, long long& p0) { b = g / ngl; p0 = (g - b * ngl) * 64; }
 
 // A 32-position tile of a (B, L, 32) token array or a (B, 32, L) plane stack in accumulator layout: register 4g + i of
 // lane (n, h) = channel 8g + 4h + i of position pq (16-byte accesses on tokens, 128-byte runs per half-wave on planes).
@@ -82,21 +126,99 @@ __device__ __forceinline__ void tile_normalise(float (&v)[16], float eps) {
     for (int i = 0; i < 16; ++i) v[i] *= r;
 }
 
+// Accumulator registers 4 gq + i <- s[STRIDE gq + i]: four ds_read_b128.  acc_rows: the registers of half h from a row of 32
+// per-channel values (a bias a product starts from, a skip scale), register 4 gq + i = channel 8 gq + 4 h + i.
+// (filled through a reference: returned by value, lfss_out_mfma_kernel came out with 17 more registers)
+template <int STRIDE>
+__device__ __forceinline__ void acc_quads(const float* s, lfss_v16f& a) {
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const float4 bb = *reinterpret_cast<const float4*>(&s[STRIDE * gq]);
+        a[4 * gq] = bb.x; a[4 * gq + 1] = bb.y; a[4 * gq + 2] = bb.z; a[4 * gq + 3] = bb.w;
+    }
+}
+__device__ __forceinline__ void acc_rows(const float* s32, int h, lfss_v16f& a) { acc_quads<8>(s32 + 4 * h, a); }
+// v = v * skip + acc in accumulator layout, in place (the block's second skip connection: v comes in as the token tile)
+__device__ __forceinline__ void skip_add(const float* s_skip, int h, lfss_v16f acc, float (&v)[16]) {
+    lfss_v16f sk;
+    acc_rows(s_skip, h, sk);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = fmaf(v[i], sk[i], acc[i]);
+}
+
 // A operands live in LDS in fetch order: operand j of lane l at s[((j >> 2) * 64 + l) * 4 + (j & 3)] - one
 // conflict-free ds_read_b128 per four MFMAs (256 B per MFMA against 64 cycles of matrix-core time).
 __device__ __forceinline__ int aop_slot(int j, int l) { return ((j >> 2) * 64 + l) * 4 + (j & 3); }
-// channel held by accumulator register j in lanes of half h
+// channel held by accumulator register j in lanes of half h = the channel K-step j of the next product carries there
 __device__ __forceinline__ int acc_chan(int j, int h) { return (j & 3) + 8 * (j >> 2) + 4 * h; }
 
-// waves per SIMD the middle kernel is compiled for.  Four (128 registers) spilled 46 vector registers of the ny = 4 fp32
-// form to scratch; three (163 registers, no spills) is 5 % faster on the kernel (6.92 -> 6.60 ms per UHD step for the
-// block glue, tools: build_variant.sh mid3, bench.py twice each, gpurun_out r3z).
-#ifndef WM_LFSS_MID_WAVES
-#define WM_LFSS_MID_WAVES 3
-#endif
-#ifndef WM_LFSS_IN_WAVES
-#define WM_LFSS_IN_WAVES 4
-#endif
+// Fill NOP operands x 64 lanes of an LDS block in fetch order (all 256 threads): operand j of lane l = rule(j, l).
+template <int NOP, typename F>
+__device__ __forceinline__ void stage_aop(float* s, F&& rule) {
+    for (int e = threadIdx.x; e < NOP * 64; e += 256) {
+        const int j = e >> 6, l = e & 63;
+        s[aop_slot(j, l)] = rule(j, l);
+    }
+}
+// NMT row blocks x 16 operands: operand 16 mt + j of lane l = rule(mt, j, l)
+template <int NMT, typename F>
+__device__ __forceinline__ void stage_aop_blocks(float* s, F&& rule) {
+    for (int e = threadIdx.x; e < NMT * 16 * 64; e += 256) {
+        const int mt = e >> 10, j = (e >> 6) & 15, l = e & 63;
+        s[aop_slot(mt * 16 + j, l)] = rule(mt, j, l);
+    }
+}
+// the row blocks of a (32 NMT, 32) matrix whose B operands are an accumulator tile: operand 16 mt + j of lane l =
+// W[32 mt + (l & 31)][k] * ln_w[k] (the LayerNorm weight folded in), k = acc_chan(j, l >> 5)
+template <int NMT>
+__device__ __forceinline__ void stage_aop_rows(float* s, const float* __restrict__ W, const float* __restrict__ ln_w) {
+    stage_aop_blocks<NMT>(s, [=](int mt, int j, int l) {
+        const int k = acc_chan(j, l >> 5);
+        return W[(32 * mt + (l & 31)) * 32 + k] * ln_w[k];
+    });
+}
+// conv3's (32, 32) weight in lfss_out's K order: operand j of lane l = W3[l & 31][acc_chan(j, l >> 5)]
+__device__ __forceinline__ void stage_W3(float* s_A3, const float* __restrict__ W3) {
+    stage_aop<16>(s_A3, [=](int j, int l) { return W3[(l & 31) * 32 + acc_chan(j, l >> 5)]; });
+}
+// a LayerNorm's bias folded into the projection after it: start + W[row] . ln_b
+__device__ __forceinline__ float folded_bias(const float* __restrict__ W, int row, const float* __restrict__ ln_b, float start) {
+    float acc = start;
+    for (int k = 0; k < 32; ++k) acc = fmaf(W[row * 32 + k], ln_b[k], acc);
+    return acc;
+}
+// the depth-wise taps of 64 channels as [channel][9 taps | bias | 0 0]: three ds_read_b128 per channel (load_dw_taps)
+__device__ __forceinline__ void stage_dw_taps(float* s_cw, const float* __restrict__ cw /*(64, 3, 3)*/, const float* __restrict__ cbias) {
+    for (int e = threadIdx.x; e < 64 * 12; e += 256) {
+        const int c = e / 12, q = e - 12 * c;
+        s_cw[e] = q < 9 ? cw[c * 9 + q] : (q == 9 && cbias ? cbias[c] : 0.0f);
+    }
+}
+__device__ __forceinline__ void load_dw_taps(const float* s_cw, int c, float (&w)[10] /* 9 taps, bias */) {
+    const float* wk = s_cw + c * 12;
+    const float4 w0 = *reinterpret_cast<const float4*>(wk), w1 = *reinterpret_cast<const float4*>(wk + 4),
+                 w2 = *reinterpret_cast<const float4*>(wk + 8);
+    w[0] = w0.x; w[1] = w0.y; w[2] = w0.z; w[3] = w0.w; w[4] = w1.x; w[5] = w1.y; w[6] = w1.z; w[7] = w1.w; w[8] = w2.x; w[9] = w2.y;
+}
+
+// THE K loop.  mfma_k4: one ds_read_b128 of A operands 4 q .. 4 q + 3 of an LDS block in fetch order - K-steps j0 .. j0 + 3 - then
+// for each K-step j the NT tiles' MFMAs in tile order, acc[t] += A_j x bop(j, t).  mfma_rows: NK4 of them from operand quad q0 on =
+// a product over 8 NK4 channels.  (bop captures its register arrays BY VALUE: by reference, the recomputing middle kernel took ten
+// more registers.)
+template <int NT, typename BF>
+__device__ __forceinline__ void mfma_k4(const float* sA, int q, int lane, int j0, BF&& bop, lfss_v16f (&acc)[NT]) {
+    const float4 a4 = *reinterpret_cast<const float4*>(&sA[(q * 64 + lane) * 4]);
+    const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t] = mfma32(av[jj], bop(j0 + jj, t), acc[t]);
+}
+template <int NK4, int NT, typename BF>
+__device__ __forceinline__ void mfma_rows(const float* sA, int q0, int lane, BF&& bop, lfss_v16f (&acc)[NT]) {
+#pragma unroll
+    for (int j4 = 0; j4 < NK4; ++j4) mfma_k4(sA, q0 + j4, lane, 4 * j4, bop, acc);
+}
 
 // two tiles' accumulators of one output row block -> 256-byte runs: after the swap, register i of `lo` is channel
 // row(i) at positions p0 .. p0 + 63 and register i of `hi` is channel row(i) + 4
@@ -116,18 +238,12 @@ __device__ __forceinline__ void store_rows64(TP* __restrict__ plane0 /* channel 
 
 // ---- lfss_mid: ysum, z, tok -> tok1 (B, L, C), f (B, D, L) -------------------------------------------
 // NY = 1: merged core output; NY = 4: the four directions' outputs, added here (:490).  TP: storage type of the y / z / f
-// planes (float, or bf16_t in the bf16-storage mode)
+// planes (float, or bf16_t in the bf16-storage mode).  (NY = 2, paired core output planes, was built and lost: DESIGN.md 4.)
 // RZ: the gate z = in_proj(ln_1(tok))[D:2D] (:485-486) is RECOMPUTED here from the token tile this kernel reads anyway for
 // the skip connection, instead of being written by lfss_in and read back (512 B per position of the block's 3456): the same
 // A operands (W_in rows D.. x ln_1.weight), the same normalised tile as B operands, the same matrix-instruction order and bias
 // start as lfss_in_mfma_kernel - bit-identical z in fp32 storage - with the output ROWS permuted so that accumulator
 // register i of row block mt IS channel 2 (16 mt + i) + h: the layout the out_norm'ed y has after its half-wave swap.
-// (the recomputing form holds the normalised token tile and the gate accumulators beside y: at three waves per SIMD it spills 19
-// registers; at two - 256 registers, none spilled - it is 3-6 % faster per call, tools/bench_lfss_rz.py with -DWM_LFSS_MID_WAVES=2;
-// the reading form is 25 % slower at two)
-#ifndef WM_LFSS_MID_RZ_WAVES
-#define WM_LFSS_MID_RZ_WAVES 2
-#endif
 template <int NY, typename TP = float, bool RZ = false>
 __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES) void lfss_mid_mfma_kernel(
     const TP* __restrict__ ysum, long long ystride, const TP* __restrict__ z, const float* __restrict__ tok, int tok_nchw,
@@ -138,6 +254,7 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
     float* __restrict__ tok1, TP* __restrict__ f, int B, long long L, int ngl, long long ngroups, int gpw,
     const float* __restrict__ ln1_w = nullptr, const float* __restrict__ ln1_b = nullptr, float ln1_eps = 0.0f,
     const float* __restrict__ W_in = nullptr /*(2D, C)*/) {
+    static_assert(NY == 1 || NY == 4, "merged or four separate core outputs");
     constexpr int C = 32, D = 64;
     __shared__ __attribute__((aligned(16))) float s_skip[C];
     __shared__ __attribute__((aligned(16))) float s_b1[D];
@@ -148,44 +265,31 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if constexpr (RZ) {
-        for (int e = threadIdx.x; e < 2 * (C / 2) * 64; e += 256) {
-            const int mt = e >> 10, j = (e >> 6) & 15, l = e & 63;
+        stage_aop_blocks<2>(s_Az, [=](int mt, int j, int l) {
             const int k = acc_chan(j, l >> 5), r = l & 31;
             const int c = 2 * (16 * mt + (r & 3) + 4 * (r >> 3)) + ((r >> 2) & 1);   // the gate channel MFMA row r of block mt computes
-            s_Az[aop_slot(mt * 16 + j, l)] = W_in[(D + c) * C + k] * ln1_w[k];
-        }
+            return W_in[(D + c) * C + k] * ln1_w[k];
+        });
         if (threadIdx.x >= 128 && threadIdx.x < 128 + D) {
             const int m = threadIdx.x - 128, hh = m >> 5, mt = (m >> 4) & 1, i = m & 15;
-            const int c = 2 * (16 * mt + i) + hh;
-            float acc = 0.0f;
-            for (int k = 0; k < C; ++k) acc = fmaf(W_in[(D + c) * C + k], ln1_b[k], acc);
-            s_bz[m] = acc;
+            s_bz[m] = folded_bias(W_in, D + 2 * (16 * mt + i) + hh, ln1_b, 0.0f);
         }
     }
     if (threadIdx.x < C) s_skip[threadIdx.x] = skip1[threadIdx.x];
     if (threadIdx.x >= 64 && threadIdx.x < 64 + D) {
         const int m = threadIdx.x - 64;
-        float acc = b1[m];
-        for (int k = 0; k < C; ++k) acc = fmaf(W1[m * C + k], ln2_b[k], acc);
-        s_b1[m] = acc;
+        s_b1[m] = folded_bias(W1, m, ln2_b, b1[m]);
     }
-    for (int e = threadIdx.x; e < (D / 2) * 64; e += 256) {
-        const int j = e >> 6, l = e & 63;
-        s_Aout[aop_slot(j, l)] = W_out[(l & 31) * D + 2 * j + (l >> 5)];
-    }
-    for (int e = threadIdx.x; e < 2 * (C / 2) * 64; e += 256) {
-        const int mt = e >> 10, j = (e >> 6) & 15, l = e & 63;
-        const int k = acc_chan(j, l >> 5);
-        s_A1[aop_slot(mt * 16 + j, l)] = W1[(32 * mt + (l & 31)) * C + k] * ln2_w[k];
-    }
+    stage_aop<D / 2>(s_Aout, [=](int j, int l) { return W_out[(l & 31) * D + 2 * j + (l >> 5)]; });
+    stage_aop_rows<2>(s_A1, W1, ln2_w);
     __syncthreads();
 
     const long long g0 = ((long long)blockIdx.x * 4 + wv) * gpw;
     for (int gi = 0; gi < gpw; ++gi) {
         const long long g = g0 + gi;
         if (g >= ngroups) break;
-        const long long b = g / ngl;
-        const long long p0 = (g - b * ngl) * 64;
+        long long b, p0;
+        group_pos(g, ngl, b, p0);
         // ---- thread-per-position: out_norm, gate ----
         const bool okl = p0 + lane < L;
         const long long pc = min(p0 + lane, L - 1);
@@ -196,16 +300,9 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
 #pragma unroll
             for (int d = 0; d < D; ++d) y[d] = ld1(yp + (long long)d * L);
         } else {
-            // the four directions' outputs, added in the reference's order y1 + y2 + y3 + y4 (:490) =
-            // [row fwd] + [row rev] + [col fwd] + [col rev]; explicit batches of 4 channels x 4 buffers in flight (8 x 4 spills at 128 registers)
-            // channels per batch of y loads (x 4 direction buffers in flight per lane).  The recomputing form runs two waves per SIMD
-            // with registers to spare: 16 channels = 64 loads in flight per lane, 0.71 -> 0.65 ms at UHD level 1 (4.9 TB/s on its
-            // 1536 B per position); 32 gains nothing more (tools/bench_lfss_rz.py with -DWM_LFSS_MID_YB_RZ=..)
-#ifndef WM_LFSS_MID_YB_RZ
-#define WM_LFSS_MID_YB_RZ 16
-#endif
-            // NY = 2 (paired core output): [row fwd + row rev] + [col fwd + col rev], twice the channels per batch = the same loads in flight
-            constexpr int YB = (RZ ? WM_LFSS_MID_YB_RZ : 4) * (NY == 2 ? 2 : 1);
+            // the four directions' outputs, added in the reference's order y1 + y2 + y3 + y4 (:490) = [row fwd] + [row rev] + [col fwd] +
+            // [col rev]; explicit batches of 4 channels x 4 buffers in flight (8 x 4 spills at 128 registers; RZ: WM_LFSS_MID_YB_RZ channels)
+            constexpr int YB = RZ ? WM_LFSS_MID_YB_RZ : 4;
 #pragma unroll
             for (int d0 = 0; d0 < D; d0 += YB) {
                 float t[NY][YB];
@@ -214,10 +311,7 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
 #pragma unroll
                     for (int i = 0; i < YB; ++i) t[q][i] = ld1(yp + q * ystride + (long long)(d0 + i) * L);
 #pragma unroll
-                for (int i = 0; i < YB; ++i) {
-                    if constexpr (NY == 2) y[d0 + i] = t[0][i] + t[1][i];
-                    else y[d0 + i] = ((t[0][i] + t[1][i]) + t[2][i]) + t[3][i];
-                }
+                for (int i = 0; i < YB; ++i) y[d0 + i] = ((t[0][i] + t[1][i]) + t[2][i]) + t[3][i];
                 __builtin_amdgcn_sched_barrier(0);       // one batch of loads in flight, not all 256 (spills)
             }
         }
@@ -237,23 +331,23 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
-        // z in explicit double-buffered batches: left to itself the compiler issues the 64 loads one at a time, each
-        // followed by its wait (64 serialised round trips per group)
-        constexpr int ZB = 8;
-        float zb[2][ZB];
+            // z in explicit double-buffered batches: left to itself the compiler issues the 64 loads one at a time, each
+            // followed by its wait (64 serialised round trips per group)
+            constexpr int ZB = 8;
+            float zb[2][ZB];
 #pragma unroll
-        for (int i = 0; i < ZB; ++i) zb[0][i] = ld1(zp + (long long)i * L);
+            for (int i = 0; i < ZB; ++i) zb[0][i] = ld1(zp + (long long)i * L);
 #pragma unroll
-        for (int d0 = 0; d0 < D; d0 += ZB) {
-            const int cur = (d0 / ZB) & 1;
-            if (d0 + ZB < D) {
+            for (int d0 = 0; d0 < D; d0 += ZB) {
+                const int cur = (d0 / ZB) & 1;
+                if (d0 + ZB < D) {
 #pragma unroll
-                for (int i = 0; i < ZB; ++i) zb[cur ^ 1][i] = ld1(zp + (long long)(d0 + ZB + i) * L);
+                    for (int i = 0; i < ZB; ++i) zb[cur ^ 1][i] = ld1(zp + (long long)(d0 + ZB + i) * L);
+                }
+#pragma unroll
+                for (int i = 0; i < ZB; ++i)
+                    y[d0 + i] = fmaf((y[d0 + i] - mean) * rstd, on_w[d0 + i], on_b[d0 + i]) * silu_fast(zb[cur][i]);
             }
-#pragma unroll
-            for (int i = 0; i < ZB; ++i)
-                y[d0 + i] = fmaf((y[d0 + i] - mean) * rstd, on_w[d0 + i], on_b[d0 + i]) * silu_fast(zb[cur][i]);
-        }
         }
         // ---- B operands of the two tiles ----
 #pragma unroll
@@ -274,22 +368,11 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
                 tile_normalise(nt, ln1_eps);
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    lfss_v16f za;
+                    lfss_v16f za[1];
+                    acc_quads<4>(&s_bz[(h * 2 + mt) * 16], za[0]);
+                    mfma_rows<C / 8>(s_Az, 4 * mt, lane, [=](int j, int) { return nt[j]; }, za);
 #pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const float4 bb = *reinterpret_cast<const float4*>(&s_bz[(h * 2 + mt) * 16 + 4 * gq]);
-                        za[4 * gq] = bb.x; za[4 * gq + 1] = bb.y; za[4 * gq + 2] = bb.z; za[4 * gq + 3] = bb.w;
-                    }
-#pragma unroll
-                    for (int j4 = 0; j4 < C / 8; ++j4) {
-                        const float4 a4 = *reinterpret_cast<const float4*>(&s_Az[((mt * 4 + j4) * 64 + lane) * 4]);
-                        const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj)
-                            za = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], nt[4 * j4 + jj], za, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) y[2 * (16 * mt + i) + t] *= silu_fast(za[i]);
+                    for (int i = 0; i < 16; ++i) y[2 * (16 * mt + i) + t] *= silu_fast(za[0][i]);
                 }
             }
         }
@@ -298,22 +381,15 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-#pragma unroll
-        for (int j4 = 0; j4 < D / 8; ++j4) {
-            const float4 a4 = *reinterpret_cast<const float4*>(&s_Aout[(j4 * 64 + lane) * 4]);
-            const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], y[2 * (4 * j4 + jj)], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], y[2 * (4 * j4 + jj) + 1], acc[1], 0, 0, 0);
-            }
-        }
+        mfma_rows<D / 8>(s_Aout, 0, lane, [=](int j, int t) { return y[2 * j + t]; }, acc);
         float tt[2][16];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const long long pos = p0 + 32 * t + n;
             const long long pq = min(pos, L - 1);
             load_tile32(tok, tok_nchw != 0, b, pq, L, h, tt[t]);
+            // skip_add, written out: through the helper the same arithmetic schedules this kernel's loads differently (8 fewer to 1
+            // more s_waitcnt in four of its eight forms)
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 const float4 sk = *reinterpret_cast<const float4*>(&s_skip[8 * gq + 4 * h]);
@@ -328,22 +404,9 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             lfss_v16f a[2];
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 bb = *reinterpret_cast<const float4*>(&s_b1[32 * mt + 8 * gq + 4 * h]);
-                a[0][4 * gq] = bb.x; a[0][4 * gq + 1] = bb.y; a[0][4 * gq + 2] = bb.z; a[0][4 * gq + 3] = bb.w;
-            }
+            acc_rows(s_b1 + 32 * mt, h, a[0]);
             a[1] = a[0];
-#pragma unroll
-            for (int j4 = 0; j4 < C / 8; ++j4) {
-                const float4 a4 = *reinterpret_cast<const float4*>(&s_A1[((mt * 4 + j4) * 64 + lane) * 4]);
-                const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    a[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], tt[0][4 * j4 + jj], a[0], 0, 0, 0);
-                    a[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], tt[1][4 * j4 + jj], a[1], 0, 0, 0);
-                }
-            }
+            mfma_rows<C / 8>(s_A1, 4 * mt, lane, [=](int j, int t) { return tt[t][j]; }, a);
             store_rows64(f + (b * D + 32 * mt) * L + p0 + lane, L, okl, a[0], a[1]);
         }
     }
@@ -361,22 +424,14 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
     __shared__ __attribute__((aligned(16))) float s_A[4 * (C / 2) * 64];         // 4 row blocks x 16 operands
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x < 2 * D) {
-        float acc = 0.0f;
-        for (int k = 0; k < C; ++k) acc = fmaf(W_in[threadIdx.x * C + k], ln_b[k], acc);
-        s_bias[threadIdx.x] = acc;
-    }
-    for (int e = threadIdx.x; e < 4 * (C / 2) * 64; e += 256) {
-        const int mt = e >> 10, j = (e >> 6) & 15, l = e & 63;
-        const int k = acc_chan(j, l >> 5);
-        s_A[aop_slot(mt * 16 + j, l)] = W_in[(32 * mt + (l & 31)) * C + k] * ln_w[k];
-    }
+    if (threadIdx.x < 2 * D) s_bias[threadIdx.x] = folded_bias(W_in, threadIdx.x, ln_b, 0.0f);
+    stage_aop_rows<4>(s_A, W_in, ln_w);
     __syncthreads();
     const long long g0 = (long long)blockIdx.x * 4 * gpw + wv;     // the block's waves walk adjacent groups together
     float nx[2][16];
     auto load_tok = [&](long long g) {
-        const long long b = g / ngl;
-        const long long p0 = (g - b * ngl) * 64;
+        long long b, p0;
+        group_pos(g, ngl, b, p0);
 #pragma unroll
         for (int t = 0; t < 2; ++t) load_tile32(tok, tok_nchw != 0, b, min(p0 + 32 * t + n, L - 1), L, h, nx[t]);
     };
@@ -384,8 +439,8 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
     for (int gi = 0; gi < gpw; ++gi) {
         const long long g = g0 + 4 * gi;
         if (g >= ngroups) break;
-        const long long b = g / ngl;
-        const long long p0 = (g - b * ngl) * 64;
+        long long b, p0;
+        group_pos(g, ngl, b, p0);
         const bool okl = p0 + lane < L;
         float a[2][16];
 #pragma unroll
@@ -399,22 +454,9 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
         for (int mt = 0; mt < 4; ++mt) {
             if (mt >= 2 && !z) break;                    // z == nullptr: the consumer recomputes the gate (lfss_mid, RZ)
             lfss_v16f acc[2];
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 bb = *reinterpret_cast<const float4*>(&s_bias[32 * mt + 8 * gq + 4 * h]);
-                acc[0][4 * gq] = bb.x; acc[0][4 * gq + 1] = bb.y; acc[0][4 * gq + 2] = bb.z; acc[0][4 * gq + 3] = bb.w;
-            }
+            acc_rows(s_bias + 32 * mt, h, acc[0]);
             acc[1] = acc[0];
-#pragma unroll
-            for (int j4 = 0; j4 < C / 8; ++j4) {
-                const float4 a4 = *reinterpret_cast<const float4*>(&s_A[((mt * 4 + j4) * 64 + lane) * 4]);
-                const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], a[0][4 * j4 + jj], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], a[1][4 * j4 + jj], acc[1], 0, 0, 0);
-                }
-            }
+            mfma_rows<C / 8>(s_A, 4 * mt, lane, [=](int j, int t) { return a[t][j]; }, acc);
             TP* dp = (mt < 2 ? x + (b * D + 32 * mt) * L : z + (b * D + 32 * (mt - 2)) * L) + p0 + lane;
             store_rows64(dp, L, okl, acc[0], acc[1]);
         }
@@ -422,6 +464,8 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
 }
 
 // ---- lfss_out: fc (B, D, L), tok1 -> tok2 --------------------------------------------------------------
+// (the A operands stay in 16 registers here: K-step j carries conv3's column acc_chan(j, h), as stage_W3 puts it in LDS
+// for the two forms below)
 template <typename TP = float>
 __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restrict__ fc, const float* __restrict__ tok1,
                                                               const float* __restrict__ W3 /*(C, C)*/,
@@ -436,20 +480,16 @@ __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restr
     if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
     float A[C / 2];
 #pragma unroll
-    for (int j = 0; j < C / 2; ++j) A[j] = W3[n * C + (j & 3) + 8 * (j >> 2) + 4 * h];
+    for (int j = 0; j < C / 2; ++j) A[j] = W3[n * C + acc_chan(j, h)];
     __syncthreads();
-    float sk[16];
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-        const float4 s4 = *reinterpret_cast<const float4*>(&s_skip[8 * gq + 4 * h]);
-        sk[4 * gq] = s4.x; sk[4 * gq + 1] = s4.y; sk[4 * gq + 2] = s4.z; sk[4 * gq + 3] = s4.w;
-    }
+    lfss_v16f sk;
+    acc_rows(s_skip, h, sk);
     const long long g0 = (long long)blockIdx.x * 4 * gpw + wv;     // the block's waves walk adjacent groups together
     for (int gi = 0; gi < gpw; ++gi) {
         const long long g = g0 + 4 * gi;
         if (g >= ngroups) break;
-        const long long b = g / ngl;
-        const long long p0 = (g - b * ngl) * 64;
+        long long b, p0;
+        group_pos(g, ngl, b, p0);
         float gate[2][16], val[2][16], tk[2][16];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -467,14 +507,9 @@ __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restr
         for (int t = 0; t < 2; ++t) {
             const long long pos = p0 + 32 * t + n;
             lfss_v16f acc;
+            acc_rows(s_b3, h, acc);
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 bb = *reinterpret_cast<const float4*>(&s_b3[8 * gq + 4 * h]);
-                acc[4 * gq] = bb.x; acc[4 * gq + 1] = bb.y; acc[4 * gq + 2] = bb.z; acc[4 * gq + 3] = bb.w;
-            }
-#pragma unroll
-            for (int j = 0; j < C / 2; ++j)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[j], gelu_erf(gate[t][j]) * val[t][j], acc, 0, 0, 0);
+            for (int j = 0; j < C / 2; ++j) acc = mfma32(A[j], gelu_erf(gate[t][j]) * val[t][j], acc);
             float o[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) o[i] = fmaf(tk[t][i], sk[i], acc[i]);
@@ -488,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restr
 // unfused pair wrote fc (256 B per position) and read it back in the next launch.  Here a wave takes 64 consecutive
 // positions, one per lane: a depth-wise tap needs no other channel, so the lane loads the nine taps of each of its 64
 // channel values itself - 256-byte coalesced runs per (channel, row, column shift), the shifted copies are first-level
-// cache hits - and reduces them in the depth-wise kernel's own order (bias, then the taps row by row).  The 32 products
+// cache hits - and reduces them in the depth-wise kernel's own order (dw_taps9).  The 32 products
 // gelu(gate) * value go to a per-wave LDS tile [channel][position], from which the two 32-position MFMA tiles read their
 // B operands in lfss_out's K order: fused and unfused results are BIT-IDENTICAL on fp32 planes.
 // Groups in which no lane sits in the first or last image column take the unmasked path; zero padding above / below the
@@ -497,6 +532,10 @@ __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restr
 // offset + immediate column shift per load, and the range check (offset >= plane bytes -> 0; a negative offset wraps to a
 // huge one) supplies the zero padding ABOVE the first and BELOW the last image row for free.  (The scalar offset operand
 // takes part in the range check on gfx950 - one descriptor over all planes + a per-channel soffset read zeros.)
+template <typename TP>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const TP* fb /* + b D L */, int c, long long L) {      // wave-uniform
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<TP*>(fb + (long long)c * L), 0, (int)(L * (int)sizeof(TP)), 0x00020000);
+}
 template <typename TP> __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int voff);
 template <> __device__ __forceinline__ float buf_ld<float>(__amdgpu_buffer_rsrc_t r, int voff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
@@ -529,8 +568,7 @@ __device__ __forceinline__ void dwconv_gate_positions(const TP* __restrict__ fb 
         for (int cc = 0; cc < 4; ++cc)
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(               // wave-uniform
-                    const_cast<TP*>(fb + (long long)(c0 + cc + 32 * v) * L), 0, (int)(L * E), 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs = plane_rsrc(fb, c0 + cc + 32 * v, L);
 #pragma unroll
                 for (int dr = 0; dr < 3; ++dr) {
                     const float a = buf_ld<TP>(rs, off[dr] - E), b = buf_ld<TP>(rs, off[dr]), e = buf_ld<TP>(rs, off[dr] + E);
@@ -542,23 +580,15 @@ __device__ __forceinline__ void dwconv_gate_positions(const TP* __restrict__ fb 
             float fc[2];
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
-                const float* wk = s_cw + (c0 + cc + 32 * v) * 12;                                    // [9 taps | bias | 0 0]
-                const float4 w0 = *reinterpret_cast<const float4*>(wk), w1 = *reinterpret_cast<const float4*>(wk + 4),
-                             w2 = *reinterpret_cast<const float4*>(wk + 8);
-                float a = w2.y;                                      // the depth-wise kernel's order: bias, then taps row by row
-                a = fmaf(w0.x, t[cc][v][0], a); a = fmaf(w0.y, t[cc][v][1], a); a = fmaf(w0.z, t[cc][v][2], a);
-                a = fmaf(w0.w, t[cc][v][3], a); a = fmaf(w1.x, t[cc][v][4], a); a = fmaf(w1.y, t[cc][v][5], a);
-                a = fmaf(w1.z, t[cc][v][6], a); a = fmaf(w1.w, t[cc][v][7], a); a = fmaf(w2.x, t[cc][v][8], a);
-                fc[v] = a;
+                float w[10];
+                load_dw_taps(s_cw, c0 + cc + 32 * v, w);
+                fc[v] = dw_taps9(w[9], w, t[cc][v], t[cc][v] + 3, t[cc][v] + 6);
             }
             sg[(c0 + cc) * 64] = gelu_erf(fc[0]) * fc[1];
         }
     }
 }
 
-#ifndef WM_LFSS_OUT_TILE
-#define WM_LFSS_OUT_TILE 8        // image rows per band of the column-major group order (0 rows = linear order: pass gpr = 0)
-#endif
 template <typename TP = float>
 __global__ __launch_bounds__(256, 4) void lfss_out_conv_mfma_kernel(
     const TP* __restrict__ f, const float* __restrict__ cw /*(D, 3, 3)*/, const float* __restrict__ cbias /*(D) or null*/,
@@ -575,14 +605,8 @@ __global__ __launch_bounds__(256, 4) void lfss_out_conv_mfma_kernel(
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
-    for (int e = threadIdx.x; e < (C / 2) * 64; e += 256) {
-        const int j = e >> 6, l = e & 63;
-        s_A3[aop_slot(j, l)] = W3[(l & 31) * C + acc_chan(j, l >> 5)];    // lfss_out's K order: bit-identical sums
-    }
-    for (int e = threadIdx.x; e < D * 12; e += 256) {
-        const int c = e / 12, q = e - 12 * c;
-        s_cw[e] = q < 9 ? cw[c * 9 + q] : (q == 9 && cbias ? cbias[c] : 0.0f);
-    }
+    stage_W3(s_A3, W3);                                              // lfss_out's K order: bit-identical sums
+    stage_dw_taps(s_cw, cw, cbias);
     __syncthreads();
     const long long g0 = (long long)blockIdx.x * 4 * gpw + wv;     // the block's waves walk adjacent groups together
     for (int gi = 0; gi < gpw; ++gi) {
@@ -618,34 +642,16 @@ __global__ __launch_bounds__(256, 4) void lfss_out_conv_mfma_kernel(
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         lfss_v16f acc[2];
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const float4 bb = *reinterpret_cast<const float4*>(&s_b3[8 * gq + 4 * h]);
-            acc[0][4 * gq] = bb.x; acc[0][4 * gq + 1] = bb.y; acc[0][4 * gq + 2] = bb.z; acc[0][4 * gq + 3] = bb.w;
-        }
+        acc_rows(s_b3, h, acc[0]);
         acc[1] = acc[0];
-#pragma unroll
-        for (int j4 = 0; j4 < C / 8; ++j4) {
-            const float4 a4 = *reinterpret_cast<const float4*>(&s_A3[(j4 * 64 + lane) * 4]);
-            const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {            // K-step j = channels acc_chan(j, h); tile 0 = positions n, tile 1 = 32 + n
-                const int ch = acc_chan(4 * j4 + jj, h);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], sg[ch * 64 + n], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], sg[ch * 64 + 32 + n], acc[1], 0, 0, 0);
-            }
-        }
+        // K-step j = channels acc_chan(j, h); tile 0 = positions n, tile 1 = 32 + n
+        mfma_rows<C / 8>(s_A3, 0, lane, [=](int j, int t) { return sg[acc_chan(j, h) * 64 + 32 * t + n]; }, acc);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const long long pos = p0 + 32 * t + n;
-            float tk[16], o[16];
-            load_tile32(tok1, false, b, min(pos, L - 1), L, h, tk);
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 s4 = *reinterpret_cast<const float4*>(&s_skip[8 * gq + 4 * h]);
-                o[4 * gq] = fmaf(tk[4 * gq], s4.x, acc[t][4 * gq]); o[4 * gq + 1] = fmaf(tk[4 * gq + 1], s4.y, acc[t][4 * gq + 1]);
-                o[4 * gq + 2] = fmaf(tk[4 * gq + 2], s4.z, acc[t][4 * gq + 2]); o[4 * gq + 3] = fmaf(tk[4 * gq + 3], s4.w, acc[t][4 * gq + 3]);
-            }
+            float o[16];
+            load_tile32(tok1, false, b, min(pos, L - 1), L, h, o);
+            skip_add(s_skip, h, acc[t], o);
             if (pos < L) store_tile32(out, out_nchw != 0, b, pos, L, h, o);
         }
     }
@@ -677,14 +683,8 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
-    for (int e = threadIdx.x; e < (C / 2) * 64; e += 256) {
-        const int j = e >> 6, l = e & 63;
-        s_A3[aop_slot(j, l)] = W3[(l & 31) * C + acc_chan(j, l >> 5)];
-    }
-    for (int e = threadIdx.x; e < D * 12; e += 256) {
-        const int c = e / 12, q = e - 12 * c;
-        s_cw[e] = q < 9 ? cw[c * 9 + q] : (q == 9 && cbias ? cbias[c] : 0.0f);
-    }
+    stage_W3(s_A3, W3);
+    stage_dw_taps(s_cw, cw, cbias);
     __syncthreads();
     const long long wk = (long long)blockIdx.x * 4 + wv;         // walk = (batch, chunk of bands, strip), strips fastest
     if (wk >= nwalks) return;
@@ -707,15 +707,10 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
             off[dr] = (int)((rowp + strip * 64 + lane) * E);
             hoff[dr] = (int)((rowp + hcol) * E);
         }
-        lfss_v16f acc[R][2];
+        lfss_v16f acc[2 * R];                                     // tile t of row rr: acc[2 rr + t]
+        acc_rows(s_b3, h, acc[0]);
 #pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const float4 bb = *reinterpret_cast<const float4*>(&s_b3[8 * gq + 4 * h]);
-            acc[0][0][4 * gq] = bb.x; acc[0][0][4 * gq + 1] = bb.y; acc[0][0][4 * gq + 2] = bb.z; acc[0][0][4 * gq + 3] = bb.w;
-        }
-        acc[0][1] = acc[0][0];
-#pragma unroll
-        for (int rr = 1; rr < R; ++rr) { acc[rr][0] = acc[0][0]; acc[rr][1] = acc[0][0]; }
+        for (int q = 1; q < 2 * R; ++q) acc[q] = acc[0];
         // (a double-buffered form - the next channel's loads in flight under this one's products - measured the same at UHD level 1
         // and 7 % slower at level 2, with four spilled registers: not kept)
 #pragma unroll 1
@@ -728,8 +723,7 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
                 for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
                     for (int v = 0; v < 2; ++v) {
-                        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(               // wave-uniform
-                            const_cast<TP*>(fb + (long long)(8 * j4 + 2 * cs + cc + 32 * v) * L), 0, (int)(L * E), 0x00020000);
+                        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(fb, 8 * j4 + 2 * cs + cc + 32 * v, L);
 #pragma unroll
                         for (int dr = 0; dr < R + 2; ++dr) {
                             ctr[cc][v][dr] = buf_ld<TP>(rs, off[dr]);
@@ -738,15 +732,9 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
                     }
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) {
-                    float w[2][12];
+                    float w[2][10];
 #pragma unroll
-                    for (int v = 0; v < 2; ++v) {
-                        const float* wk9 = s_cw + (8 * j4 + 2 * cs + cc + 32 * v) * 12;                     // [9 taps | bias | 0 0]
-                        const float4 w0 = *reinterpret_cast<const float4*>(wk9), w1 = *reinterpret_cast<const float4*>(wk9 + 4),
-                                     w2 = *reinterpret_cast<const float4*>(wk9 + 8);
-                        w[v][0] = w0.x; w[v][1] = w0.y; w[v][2] = w0.z; w[v][3] = w0.w; w[v][4] = w1.x; w[v][5] = w1.y;
-                        w[v][6] = w1.z; w[v][7] = w1.w; w[v][8] = w2.x; w[v][9] = w2.y;
-                    }
+                    for (int v = 0; v < 2; ++v) load_dw_taps(s_cw, 8 * j4 + 2 * cs + cc + 32 * v, w[v]);
                     float t[2][R + 2][3];
 #pragma unroll
                     for (int v = 0; v < 2; ++v)
@@ -761,12 +749,7 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
                     for (int rr = 0; rr < R; ++rr) {
                         float fc[2];
 #pragma unroll
-                        for (int v = 0; v < 2; ++v) {
-                            float a = w[v][9];                       // the depth-wise kernel's order: bias, then taps row by row
-#pragma unroll
-                            for (int k = 0; k < 9; ++k) a = fmaf(w[v][k], t[v][rr + k / 3][k % 3], a);
-                            fc[v] = a;
-                        }
+                        for (int v = 0; v < 2; ++v) fc[v] = dw_taps9(w[v][9], w[v], t[v][rr], t[v][rr + 1], t[v][rr + 2]);
                         sg[((2 * cs + cc) * R + rr) * 64 + lane] = gelu_erf(fc[0]) * fc[1];
                     }
                 }
@@ -774,17 +757,8 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const float4 a4 = *reinterpret_cast<const float4*>(&s_A3[(j4 * 64 + lane) * 4]);
-            const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {                      // K-step j = 4 j4 + jj: channels acc_chan(j, h) = 8 j4 + jj + 4 h
-                const float* sr = sg + ((jj + 4 * h) * R) * 64;
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) {
-                    acc[rr][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], sr[rr * 64 + n], acc[rr][0], 0, 0, 0);
-                    acc[rr][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[jj], sr[rr * 64 + 32 + n], acc[rr][1], 0, 0, 0);
-                }
-            }
+            // K-step 4 j4 + jj: channels acc_chan(4 j4 + jj, h) = 8 j4 + jj + 4 h, the group's gated channel jj + 4 h
+            mfma_k4(s_A3, j4, lane, 0, [=](int jj, int q) { const float* sr = sg + ((jj + 4 * h) * R) * 64; return sr[32 * q + n]; }, acc);
         }
 #pragma unroll
         for (int rr = 0; rr < R; ++rr) {
@@ -793,14 +767,9 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt) {
                     const long long pos = p0 + 32 * tt + n;
-                    float tk[16], o[16];
-                    load_tile32(tok1, false, b, pos, L, h, tk);
-#pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const float4 s4 = *reinterpret_cast<const float4*>(&s_skip[8 * gq + 4 * h]);
-                        o[4 * gq] = fmaf(tk[4 * gq], s4.x, acc[rr][tt][4 * gq]); o[4 * gq + 1] = fmaf(tk[4 * gq + 1], s4.y, acc[rr][tt][4 * gq + 1]);
-                        o[4 * gq + 2] = fmaf(tk[4 * gq + 2], s4.z, acc[rr][tt][4 * gq + 2]); o[4 * gq + 3] = fmaf(tk[4 * gq + 3], s4.w, acc[rr][tt][4 * gq + 3]);
-                    }
+                    float o[16];
+                    load_tile32(tok1, false, b, pos, L, h, o);
+                    skip_add(s_skip, h, acc[2 * rr + tt], o);
                     store_tile32(out, out_nchw != 0, b, pos, L, h, o);
                 }
             }
