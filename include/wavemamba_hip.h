@@ -202,6 +202,17 @@ int wm_lfss_mid_rz_fwd(const void* ysum, int ny, int64_t ystride, const float* t
 int wm_lfss_out_fwd(const void* fc, const float* tok1, const float* conv3_weight, const float* conv3_bias,
                     const float* skip_scale2, float* out, int out_nchw, int B, int64_t L, int C, int plane_dtype,
                     void* stream);
+/* SS2D's prologue in one kernel (wavemamba_arch.py:483-487 behind ln_1, :524): wm_lfss_in_fwd(z = NULL) with the depth-wise 3x3
+ * (conv2d, :486) and SiLU (:487) of wm_dwconv3x3_fwd(act = 1) folded in - tok -> xc = silu(conv2d(in_proj(ln_1(tok))[..., :D])) as
+ * (B, 2C, H, W) fp32 planes; x itself never exists in HBM (-512 B per position, one launch less per LFSSBlock).  Bit-identical to the
+ * two calls.  C == 32, plane_dtype == WM_F32, W % 32 == 0 and H W <= 2^23 only (WM_EUNSUPPORTED otherwise: use the two calls).
+ * conv_weight (2C, 1, 3, 3); conv_bias (2C) or NULL.
+ * wm_lfss_in_conv_band_rows: host only - the output rows a wave walks per band at this shape (every band recomputes two more rows
+ * of x); negative status outside the domain. */
+int wm_lfss_in_conv_fwd(const float* tok, int tok_nchw, const float* ln_w, const float* ln_b, float ln_eps,
+                        const float* in_proj_weight, const float* conv_weight, const float* conv_bias, float* xc,
+                        int B, int H, int W, int C, int plane_dtype, void* stream);
+int wm_lfss_in_conv_band_rows(int B, int H, int W);
 /* wm_lfss_out_fwd with the gated ffn's depth-wise 3x3 (conv2, wavemamba_arch.py:220, :226) folded in: takes conv1's
  * output planes f (B, 2C, H, W) instead of conv2's, so `fc` never exists in HBM (-512 B per position, one launch less
  * per LFSSBlock).  Bit-identical to wm_dwconv3x3_fwd(act = none) + wm_lfss_out_fwd on fp32 planes.

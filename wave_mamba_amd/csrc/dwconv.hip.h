@@ -37,12 +37,14 @@ __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + e
 // The depth-wise sum of one output value in its ONE order: bias, then the taps row by row.  w: 9 taps; r0 / r1 / r2: the three
 // input rows' values left, centre, right.  dwconv3x3_kernel and the closing LFSS kernels that fold this convolution in
 // (lfss_mfma.hip.h) all form the sum here, which is what keeps the fused and unfused paths bit-identical.
-__device__ __forceinline__ float dw_taps9(float bias, const float* w, const float* r0, const float* r1, const float* r2) {
-    float acc = bias;
-    acc = fmaf(w[0], r0[0], acc); acc = fmaf(w[1], r0[1], acc); acc = fmaf(w[2], r0[2], acc);
-    acc = fmaf(w[3], r1[0], acc); acc = fmaf(w[4], r1[1], acc); acc = fmaf(w[5], r1[2], acc);
-    acc = fmaf(w[6], r2[0], acc); acc = fmaf(w[7], r2[1], acc); acc = fmaf(w[8], r2[2], acc);
+// dw_taps3 is one kernel row of that chain (w: the row's three taps, r: left, centre, right): a kernel that meets the input rows one
+// at a time (lfss_in_conv_mfma_kernel) continues the chain of three output rows with each, and ends on the same bits.
+__device__ __forceinline__ float dw_taps3(float acc, const float* w, const float* r) {
+    acc = fmaf(w[0], r[0], acc); acc = fmaf(w[1], r[1], acc); acc = fmaf(w[2], r[2], acc);
     return acc;
+}
+__device__ __forceinline__ float dw_taps9(float bias, const float* w, const float* r0, const float* r1, const float* r2) {
+    return dw_taps3(dw_taps3(dw_taps3(bias, w, r0), w + 3, r1), w + 6, r2);
 }
 
 // TP: storage type of the x / y planes (float, or bf16_t in the bf16-storage mode: fp32 arithmetic either way)

@@ -155,6 +155,41 @@ int wm_lfss_in_fwd(const float* tok, int tok_nchw, const float* ln_w, const floa
     });
 }
 
+// wm_lfss_in_fwd(z = NULL) + wm_dwconv3x3_fwd(act = SiLU) in one kernel (lfss_in_conv_mfma_kernel): C == 32, fp32 planes, W % 32 == 0
+// (the widths the block's other folded convolution, wm_lfss_out_conv_fwd, serves) and at most 2^23 positions per image (32-bit byte
+// offsets inside a half's 32 planes).  WM_EUNSUPPORTED otherwise: callers keep the two calls.
+static bool lfss_in_conv_domain(int H, int W, int C, int plane_dtype) {
+    return C == 32 && plane_dtype == WM_F32 && W % 32 == 0 && (long long)H * W <= (1ll << 23);
+}
+
+int wm_lfss_in_conv_band_rows(int B, int H, int W) {
+    if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (!lfss_in_conv_domain(H, W, 32, WM_F32)) return WM_EUNSUPPORTED;
+    return lfss_in_conv_band_rows(B, H, W);
+}
+
+int wm_lfss_in_conv_fwd(const float* tok, int tok_nchw, const float* ln_w, const float* ln_b, float ln_eps,
+                        const float* in_proj_weight, const float* conv_weight, const float* conv_bias, float* xc, int B, int H, int W,
+                        int C, int plane_dtype, void* stream) {
+    if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (!lfss_in_conv_domain(H, W, C, plane_dtype)) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!tok || !ln_w || !ln_b || !in_proj_weight || !conv_weight || !xc) return WM_ENULL;
+    if (!tok_nchw && !aligned16(tok)) return WM_EALIGN;
+    const int nstrips = (W + kInConvCols - 1) / kInConvCols, rb = lfss_in_conv_band_rows(B, H, W), nbands = (H + rb - 1) / rb;
+    const long long nwalks = (long long)B * nbands * nstrips;
+    const dim3 grid((unsigned)((nwalks + 1) / 2));
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(5, st);
+    if (tok_nchw)
+        hipLaunchKernelGGL(lfss_in_conv_mfma_kernel<true>, grid, dim3(256), 0, st, tok, ln_w, ln_b, ln_eps, in_proj_weight, conv_weight,
+                           conv_bias, xc, B, H, W, nstrips, nbands, rb, nwalks);
+    else
+        hipLaunchKernelGGL(lfss_in_conv_mfma_kernel<false>, grid, dim3(256), 0, st, tok, ln_w, ln_b, ln_eps, in_proj_weight, conv_weight,
+                           conv_bias, xc, B, H, W, nstrips, nbands, rb, nwalks);
+    return launch_status();
+}
+
 int wm_lfss_mid_fwd(const void* ysum_, int ny, int64_t ystride, const void* z_, const float* tok, int tok_nchw, const float* out_norm_w,
                     const float* out_norm_b, float out_norm_eps, const float* out_proj_weight,
                     const float* skip_scale, const float* ln2_w, const float* ln2_b, float ln2_eps,

@@ -18,7 +18,7 @@
 // (DESIGN.md 4): loads are issued in explicit batches ahead of their use and ahead of the group's stores.
 // Reference: basicsr/archs/wavemamba_arch.py :491-494 (SS2D tail), :525-526 (LFSSBlock), :226-230 (ffn).
 //
-// The five kernels are built from these pieces (each written once, with its layout comment):
+// The six kernels are built from these pieces (each written once, with its layout comment):
 //   group_pos                          group number -> batch image and first position
 //   load_tile32 / store_tile32         a 32-position tile of tokens or planes <-> accumulator layout
 //   tile_normalise, xhalf_sum          LayerNorm statistics over a tile's 16 + 16 registers
@@ -29,8 +29,10 @@
 //                                      projection runs through it, so lfss_out's K order (acc_chan) is the same in
 //                                      lfss_out_mfma, lfss_out_conv_mfma and lfss_out_conv_acc by construction
 //   store_rows64                       two tiles of a row block -> 256-byte runs of a plane
-//   plane_rsrc, buf_ld, load_dw_taps   one channel plane as a raw buffer; a channel's taps from LDS
-//   dw_taps9 (dwconv.hip.h)            the depth-wise sum in the depth-wise kernel's own order
+//   raw_rsrc, plane_rsrc, buf_ld, load_dw_taps   memory / one channel plane as a raw buffer; a channel's taps from LDS
+//   dw_taps9, dw_taps3 (dwconv.hip.h)  the depth-wise sum in the depth-wise kernel's own order; one kernel row of it (lfss_in_conv
+//                                      continues three output rows' chains with each x row)
+//   lfss_in_conv_band_rows             rows per band of lfss_in_conv (host)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "haar.hip.h"          // bf16_t, ld1 / st1 (fp32 and bf16 overloads)
@@ -71,6 +73,13 @@ __device__ __forceinline__ float silu_fast(float v) {
 }
 __device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32); }
 __device__ __forceinline__ lfss_v16f mfma32(float a, float b, lfss_v16f acc) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0); }
+
+// `bytes` of memory from `p` as a raw buffer (the one place the descriptor's flags word is written): a load or store whose offset is
+// >= bytes reads zero / is dropped
+template <typename TP>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const TP* p, int bytes) {                                 // wave-uniform
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<TP*>(p), 0, bytes, 0x00020000);
+}
 
 // waves each take `gpw` consecutive groups of 64 positions; chosen so that the waves fill whole rounds of the
 // `slots` resident waves (1024 SIMDs x the kernel's waves per SIMD), at most 8 groups per wave
@@ -463,6 +472,148 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
     }
 }
 
+// ---- lfss_in_conv: tok -> xc = silu(dwconv3x3(x) + bias) (B, D, H, W); x never reaches memory ---------------------------
+// SS2D's prologue in one kernel (reference :483-487 behind ln_1: in_proj, chunk, NHWC -> NCHW, depth-wise 3x3, SiLU).  lfss_in wrote
+// x = in_proj(ln_1(tok))[:D] and dwconv3x3 read it back: 512 of the pair's 896 B per position.  The convolution needs x on a one-pixel
+// halo and x is a projection OUTPUT, so the halo is RECOMPUTED by the same matrix instructions:
+//   * a wave owns a strip of kInConvCols = 62 output columns - its 64 lanes are 64 consecutive image columns, one halo column each
+//     side - x a band of `rb` output rows (lfss_in_conv_band_rows) x 32 of the 64 channels (wave & 1), and walks the band's rb + 2 x
+//     rows top to bottom;
+//   * per x row: the 64 columns' tokens (load_tile32) -> tile_normalise -> the x rows of in_proj through mfma_rows with lfss_in's A
+//     operands, K order and bias start (identical x bits) -> permlane32_swap: 32 registers, lane = column;
+//   * the taps: the horizontal neighbours are the adjacent LANES (DPP wave shifts), the vertical direction is THREE running chains
+//     per channel: x row r ends output row r - 1 with kernel row 2 (SiLU, store), continues output row r with kernel row 1 and
+//     starts output row r + 1 from the bias with kernel row 0 (dw_taps3) - each output is dw_taps9's one fmaf chain, so `xc` is
+//     BIT-IDENTICAL to the pair's on fp32 planes.  Zero padding (rows and columns outside the image) enters the chains as zero
+//     operands, selected where the x row is consumed.
+// The row loop has no lane-divergent branch and no branch at all around memory operations: token loads come from clamped addresses,
+// stores are raw buffer stores whose offset is out of range for a halo lane, a column past the image or a row outside the band; the
+// token rows are loaded TWO x rows ahead (two register buffers, the loop unrolled by two), issued before the row's 32 stores.
+// Columns: round 4's overlapping 62-column strips (248-byte store runs) are what is built; the aligned 64-column form with the two outer
+// columns from a third MFMA tile (+50 % matrix, LayerNorm and token-load work per row) was not built, so not measured: OPEN WORK - the
+// 248-byte misaligned store runs may be why the kernel moves its bytes at 2.7-2.9 TB/s and not at lfss_in's 3.8.
+// 220 / 224 registers, nothing spilled (tools/kernel_resources.py); in the loop one vmcnt(62) per x row in the NCHW form and counts of
+// 40-47 / 62 in the token-row form (tools/isa_load_waits.py): no full wait.
+// Per call, wm_lfss_in_fwd(z = NULL) + wm_dwconv3x3_fwd(silu) -> this kernel, median of 7 x 20 alternating calls, NCHW / token-row input
+// (tools/bench_lfss_in_conv.py, profiles/lfss_in_conv/per_call.txt):
+//   UHD level 1 (1088 x 1920, 34-row bands)  0.431 -> 0.297 ms / 0.455 -> 0.277 ms   (2.7-2.9 TB/s on 384 B per position)
+//   UHD level 2 ( 544 x  960, 10-row bands)  0.119 -> 0.091 ms / 0.126 -> 0.088 ms
+//   UHD level 3 ( 272 x  480,  8-row bands)  0.037 -> 0.049 ms / 0.038 -> 0.048 ms: slower - the operator layer keeps the pair there
+constexpr int kInConvCols = 62;                             // output columns per strip
+constexpr int kInConvMinBand = 8, kInConvMaxBand = 64;      // output rows per band (two more x rows are recomputed per band)
+// rows per band.  A workgroup is two strips x two channel halves at two waves per SIMD, so the chip holds 512 workgroups at a time and
+// a launch lasts about rounds x (rb + 2 x rows + one of prologue): the even rb in [8, 64] with the smallest such product (UHD level 1:
+// 34 rows, 32 bands, 496 workgroups - one round).  Small maps get kInConvMinBand.
+inline int lfss_in_conv_band_rows(int B, int H, int W) {
+    const long long nstrips = (W + kInConvCols - 1) / kInConvCols;
+    int rb = kInConvMinBand;
+    long long best = -1;
+    for (int cand = kInConvMinBand; cand <= kInConvMaxBand; cand += 2) {
+        const long long nb = (H + cand - 1) / cand, wgs = ((long long)B * nstrips * nb + 1) / 2;
+        const long long cost = ((wgs + 511) / 512) * (cand + 3);
+        if (best < 0 || cost < best) { best = cost; rb = cand; }
+    }
+    return rb;
+}
+
+template <bool NCHW>
+__global__ __launch_bounds__(256, 2) void lfss_in_conv_mfma_kernel(
+    const float* __restrict__ tok, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+    const float* __restrict__ W_in /*(2D, C)*/, const float* __restrict__ cw /*(D, 3, 3)*/, const float* __restrict__ cb /*(D) or null*/,
+    float* __restrict__ xc, int B, int H, int W, int nstrips, int nbands, int rb, long long nwalks) {
+    constexpr int C = 32, D = 64;
+    __shared__ __attribute__((aligned(16))) float s_bias[D];
+    __shared__ __attribute__((aligned(16))) float s_A[2 * (C / 2) * 64];         // the x half: 2 row blocks x 16 operands
+    __shared__ __attribute__((aligned(16))) float s_cw[D * 12];                  // [channel][9 taps | bias | 0 0]
+    const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x < D) s_bias[threadIdx.x] = folded_bias(W_in, threadIdx.x, ln_b, 0.0f);
+    stage_aop_rows<2>(s_A, W_in, ln_w);
+    stage_dw_taps(s_cw, cw, cb);
+    __syncthreads();
+    const long long L = (long long)H * W;
+    const long long wk = (long long)blockIdx.x * 2 + (wv >> 1);  // walk = (batch, band, strip), strips fastest
+    const int hb = wv & 1;                                       // channel half: x channels 32 hb .. 32 hb + 31
+    if (wk >= nwalks) return;
+    const int strip = (int)(wk % nstrips);
+    const int band = (int)((wk / nstrips) % nbands);
+    const long long b = wk / ((long long)nstrips * nbands);
+    const int col0 = strip * kInConvCols - 1;                    // image column of lane 0
+    const int col = col0 + lane;
+    const bool colin = col >= 0 && col < W;
+    const bool st_ok = lane >= 1 && lane <= kInConvCols && col < W;
+    const int r0 = band * rb, r_end = min(H, r0 + rb);
+    // the half's 32 output planes as one raw buffer: lane offset + per-channel scalar offset, out of range = not written
+    const int plane_bytes = (int)(L * 4), nrec = 32 * plane_bytes;
+    const __amdgpu_buffer_rsrc_t rs = raw_rsrc(xc + (b * D + 32 * hb) * L, nrec);
+    const unsigned lane_off = st_ok ? (unsigned)(col * 4) : (unsigned)nrec;
+
+    // the chains of output rows r + 1 (P0: bias + kernel row 0 so far) and r (P1: + kernel row 1) per channel of the half; index
+    // 2 i + half = channel 8 (i >> 2) + (i & 3) + 4 half, the order the swapped accumulator registers come in
+    float P0[32], P1[32];
+#pragma unroll
+    for (int q = 0; q < 32; ++q) { P0[q] = 0.0f; P1[q] = 0.0f; }   // (the band's first two x rows end and continue rows above it: not stored)
+
+    auto load_row = [&](int rho, float (&nx)[2][16]) {           // clamped: a row outside the image or a column outside it is masked when consumed
+        const long long prow = (long long)min(max(rho, 0), H - 1) * W;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) load_tile32(tok, NCHW, b, prow + min(max(col0 + 32 * t + n, 0), W - 1), L, h, nx[t]);
+    };
+    float a[2][16];                                              // the x row's normalised tokens: B operands
+    auto consume = [&](const float (&nx)[2][16]) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) a[t][i] = nx[t][i];
+            tile_normalise(a[t], eps);
+        }
+    };
+    auto step = [&](int rho, float (&nx)[2][16]) {               // x row rho (consumed into `a`) enters the window; output row rho - 1 leaves
+        load_row(rho + 2, nx);                                   // two rows ahead, ahead of this row's 32 stores
+        __builtin_amdgcn_sched_barrier(0);
+        lfss_v16f acc[2];
+        acc_rows(s_bias + 32 * hb, h, acc[0]);
+        acc[1] = acc[0];
+        mfma_rows<C / 8>(s_A, 4 * hb, lane, [=](int j, int t) { return a[t][j]; }, acc);
+        const bool keep = colin && rho >= 0 && rho < H;          // else: zero padding
+        const bool orow = rho - 1 >= r0 && rho - 1 < r_end;      // (wave-uniform)
+        const int voff = (int)(lane_off + (orow ? (unsigned)((rho - 1) * W * 4) : (unsigned)nrec));   // scalar select + one add: >= nrec = dropped
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[0][i]), __float_as_uint(acc[1][i]), false, false);
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const int q = 2 * i + half, ch = 8 * (i >> 2) + (i & 3) + 4 * half;
+                const float xm = keep ? __uint_as_float(r[half]) : 0.0f;
+                const float t3[3] = {dpp_from_lower_lane(0.0f, xm), xm, dpp_from_upper_lane(0.0f, xm)};
+                float w[10];
+                load_dw_taps(s_cw, 32 * hb + ch, w);
+                const float o = dw_taps3(P1[q], w + 6, t3);
+                P1[q] = dw_taps3(P0[q], w + 3, t3);
+                P0[q] = dw_taps3(w[9], w, t3);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(silu_f(o)), rs, voff, ch * plane_bytes, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);                   // two channels' taps in registers at a time (all 32 hoisted: 380 spilled)
+        }
+    };
+    float nxa[2][16], nxb[2][16];
+    load_row(r0 - 1, nxa);
+    __builtin_amdgcn_sched_barrier(0);       // in the loop's order: issued the other way round, the first row's wait in the loop is for everything
+    load_row(r0, nxb);
+    __builtin_amdgcn_sched_barrier(0);
+    // The loop is rotated: a pass ENDS with the wait for the row its next pass multiplies.  Entered at that wait, the count would have
+    // to be written for the entry from the two loads above as well - one that, on every later pass, also waits out the 32 stores
+    // issued just before it.
+    consume(nxa);
+#pragma unroll 1
+    for (int rho = r0 - 1; rho <= r_end; rho += 2) {             // (an odd count's last step is one row past the band: nothing stored)
+        step(rho, nxa);
+        consume(nxb);
+        step(rho + 1, nxb);
+        consume(nxa);
+    }
+}
+
 // ---- lfss_out: fc (B, D, L), tok1 -> tok2 --------------------------------------------------------------
 // (the A operands stay in 16 registers here: K-step j carries conv3's column acc_chan(j, h), as stage_W3 puts it in LDS
 // for the two forms below)
@@ -534,7 +685,7 @@ __global__ __launch_bounds__(256, 2) void lfss_out_mfma_kernel(const TP* __restr
 // takes part in the range check on gfx950 - one descriptor over all planes + a per-channel soffset read zeros.)
 template <typename TP>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const TP* fb /* + b D L */, int c, long long L) {      // wave-uniform
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<TP*>(fb + (long long)c * L), 0, (int)(L * (int)sizeof(TP)), 0x00020000);
+    return raw_rsrc(fb + (long long)c * L, (int)(L * (int)sizeof(TP)));
 }
 template <typename TP> __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int voff);
 template <> __device__ __forceinline__ float buf_ld<float>(__amdgpu_buffer_rsrc_t r, int voff) {

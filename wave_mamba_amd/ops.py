@@ -558,11 +558,28 @@ def _w(t):
 
 
 _FUSE_OUT_CONV = True      # tests / tools: False takes wm_dwconv3x3_fwd + wm_lfss_out_fwd (bit-identical on fp32 planes)
-# (ln_1 -> in_proj -> depth-wise 3x3 -> SiLU as ONE kernel was built in round 4 - wm_lfss_in_conv_fwd, parity-green - and measured
-# 44 % slower than the two streaming kernels, profiles/r04/lfss_prologue_one_kernel.txt; deleted in round 5.)
+# ln_1 -> in_proj -> depth-wise 3x3 -> SiLU as ONE kernel (wm_lfss_in_conv_fwd: x = in_proj(ln_1(tok))[:D] never reaches HBM, 512 B
+# per position fewer; bit-identical on fp32 planes).  It needs the recomputed gate (nothing writes z on that path) and fp32 planes
+# (bf16-plane mode rounds x after lfss_in: tests/test_bf16_planes.py).  False: wm_lfss_in_fwd + wm_dwconv3x3_fwd, tests and tools.
+_FUSE_IN_CONV = True
+# The maps the one-kernel prologue takes: those the entry supports (W % 32 == 0, H W <= 2^23) with at least as many positions PER IMAGE
+# as the smallest map at which it measured faster (UHD level 2; the kernel's bands and strips are laid out per image, and only B = 1
+# was measured).  Per call, pair -> fused, median of 7 x 20 calls with [slowest fused, fastest pair], NCHW / token-row input
+# (tools/bench_lfss_in_conv.py, profiles/lfss_in_conv/per_call.txt):
+#   UHD level 1 (1088 x 1920)  0.431 -> 0.297 ms [0.323, 0.431] / 0.455 -> 0.277 ms [0.292, 0.452]
+#   UHD level 2 ( 544 x  960)  0.119 -> 0.091 ms [0.093, 0.119] / 0.126 -> 0.088 ms [0.088, 0.126]
+#   UHD level 3 ( 272 x  480)  0.037 -> 0.049 ms: 136 workgroups of long-lived waves leave half the chip idle - the pair stays
+# No map between levels 3 and 2 was measured: those keep the pair until one is.
+_FUSE_IN_CONV_MIN_POSITIONS = 544 * 960
 # The gate z = in_proj(ln_1(x))[D:] recomputed by lfss_mid from the tokens instead of written by lfss_in and read back
 # (512 of the block's 3456 B per position; bit-identical in fp32 planes: tests/test_gpu_parity.py).  0: round-3 data flow.
 _RECOMPUTE_Z = True
+
+
+def _fuse_in_conv_map(B, H, W):
+    """Maps on which lfss_block_forward takes wm_lfss_in_conv_fwd: inside the entry's domain and, per image, at least as large as
+    the smallest map at which it measured faster than the pair."""
+    return B > 0 and W % 32 == 0 and _FUSE_IN_CONV_MIN_POSITIONS <= H * W <= (1 << 23)
 
 
 def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
@@ -584,6 +601,8 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
     # C == 32: the gate z is recomputed by the block's middle kernel from the tokens it reads anyway (wm_lfss_mid_rz_fwd, bit-identical
     # in fp32 planes) - lfss_in writes the x half only (ops._RECOMPUTE_Z = False: the written / re-read z, tests and tools)
     rz = C == 32 and _RECOMPUTE_Z
+    # SS2D's prologue as one kernel: x (in_proj's first half) never reaches HBM
+    fuse_in = rz and _FUSE_IN_CONV and pd == torch.float32 and _fuse_in_conv_map(B, H, W)
     # the ffn's depth-wise 3x3 inside the closing kernel: fc (conv2's output) never reaches HBM
     fuse_out = C == 32 and W % 32 == 0 and _FUSE_OUT_CONV
     # the parameters the block's own launches read, each normalised once per call (nothing is kept across calls: a write through
@@ -597,9 +616,14 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
     tail = (_w(ff.conv3.weight), _w(ff.conv3.bias), _w(blk.skip_scale2))
 
     z = None if rz else torch.empty((B, D, L), dtype=pd, device=dev)
-    x = torch.empty((B, D, H, W), dtype=pd, device=dev)
-    _launch(dev, "wm_lfss_in_fwd", tok, int(tok_nchw), *ln1, x, z, B, L, C, code)
-    xc = dwconv3x3(x, ss.conv2d.weight, ss.conv2d.bias, "silu")
+    if fuse_in:
+        xc = torch.empty((B, D, H, W), dtype=pd, device=dev)
+        _launch(dev, "wm_lfss_in_conv_fwd", tok, int(tok_nchw), *ln1, _w(ss.conv2d.weight),
+                None if ss.conv2d.bias is None else _w(ss.conv2d.bias), xc, B, H, W, C, code)
+    else:
+        x = torch.empty((B, D, H, W), dtype=pd, device=dev)
+        _launch(dev, "wm_lfss_in_fwd", tok, int(tok_nchw), *ln1, x, z, B, L, C, code)
+        xc = dwconv3x3(x, ss.conv2d.weight, ss.conv2d.bias, "silu")
     # the four directions' outputs stay separate (one (4, B, D, L) allocation); lfss_mid adds them as it loads (:490)
     ny = 4
     y4 = _ss2d_core_fwd([xc] + core_w, merged=0, prepared=_ss2d_core_prepared(core_params))
