@@ -367,6 +367,24 @@ int wm_conv2d_wgrad(const float* gy, const float* x, float* dW, float* db, void*
 int wm_l1_mean_fwd(const float* a, const float* b, float* out, int64_t n, void* stream);
 int wm_l1_mean_bwd(const float* a, const float* b, const float* gout, float* ga, int64_t n, void* stream);
 
+/* The SSIM training loss: SSIM(window_size = 11, size_average = True) of basicsr/models/cal_ssim.py:17-35, :39-64 - what
+ * FeMaSRModel builds as self.ssim (basicsr/models/femasr_model.py:29, :172) and options/train_wavemamba_uhdll.yml:99-100 weights
+ * (pixel_ssim_opt) - csrc/ssim_loss.hip.h.  a, b: `planes` (= B C) dense fp32 planes of H x W, any H, W >= 1.  Per plane the five
+ * moments mu1, mu2, e11, e22, e12 with the 11 x 11 Gaussian of sigma 1.5 (cal_ssim.py:7-15: float32 taps) and ZERO padding of 5,
+ * S = (2 mu1 mu2 + C1)(2 (e12 - mu1 mu2) + C2) / ((mu1^2 + mu2^2 + C1)((e11 - mu1^2) + (e22 - mu2^2) + C2)), C1 = 0.01^2,
+ * C2 = 0.03^2; out[0] = the mean of S over all planes and pixels (float64 accumulation; identical inputs give exactly 1).
+ *   wm_ssim_mean_fwd: two launches, no atomics, no memset, deterministic.  workspace: wm_ssim_workspace_bytes(planes, H, W) bytes,
+ *     8-byte aligned, written before it is read (0 = invalid shape, or more than 2^24 - 1 tiles: WM_EUNSUPPORTED).  For a gradient
+ *     pass q and r (each planes H W floats: dS/de11 = dS/de22 and dS/de12) with p1 and / or p2 (dS/dmu1, dS/dmu2); all four NULL
+ *     stores nothing.
+ *   wm_ssim_mean_bwd: gx = gout[0] / n * [ w * p + 2 x (w * q) + other (w * r) ], n = planes H W, gout one device float: the
+ *     gradient for a is (x = a, other = b, p = p1), for b (x = b, other = a, p = p2).  One launch. */
+size_t wm_ssim_workspace_bytes(int64_t planes, int H, int W);
+int wm_ssim_mean_fwd(const float* a, const float* b, float* out, float* p1, float* p2, float* q, float* r, void* workspace,
+                     size_t workspace_bytes, int64_t planes, int H, int W, void* stream);
+int wm_ssim_mean_bwd(const float* x, const float* other, const float* p, const float* q, const float* r, const float* gout,
+                     float* gx, int64_t planes, int H, int W, void* stream);
+
 /* Image-quality metrics of the reference's evaluation loop (inference_wavemamba.py:116-117, :133-134 -> comput_psnr_ssim.py with
  * crop_border, input_order 'HWC' / 'CHW', test_y_channel = True), csrc/metrics.hip.h.
  *   Images: N uint8 images of H x W x 3, element (n, h, w, ch) at n sn + h sh + w sw + ch sc (strides in elements, >= 0: HWC and

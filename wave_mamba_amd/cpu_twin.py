@@ -107,3 +107,36 @@ def ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
     back = out[:, 2:4].flip(-1)
     to_rows = lambda t: t.reshape(B, D, W, H).transpose(2, 3).reshape(B, D, L)
     return out[:, 0], back[:, 0], to_rows(out[:, 1]), to_rows(back[:, 1])
+
+
+def ssim_window_1d():
+    """The 11-tap window of the SSIM training loss as cal_ssim.py builds it (gaussian(11, 1.5), :7-9): exp(-(i - 5)^2 / 4.5)
+    evaluated and normalised in FLOAT32.  The float32 taps sum to 1 - 3.1e-8, and flat bright regions feel that (sigma^2 + C2
+    is 9e-4 there, against a 2-D window sum that moves mu^2 by 7e-8), so the taps are kept exactly as the reference has them."""
+    g = torch.tensor([-(i - 5) ** 2 / 4.5 for i in range(11)], dtype=torch.float64).exp().float()
+    return g / g.sum()
+
+
+def ssim_mean(img1, img2):
+    """SSIM(window_size=11, size_average=True) of cal_ssim.py (:17-35, :39-64) for (B, C, H, W) tensors of any float dtype and
+    device: the mean over every plane and pixel of
+        S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),   C1 = 0.01^2, C2 = 0.03^2,
+    the five moments taken with the zero-padded 11 x 11 Gaussian, here as a row pass and a column pass.  Evaluated in float64
+    (as the HIP kernels accumulate: the reference's float32 loses e11 - mu1^2 on flat bright regions) and returned in the
+    inputs' dtype; differentiable by autograd."""
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise RuntimeError(f"ssim_mean: expected two (B, C, H, W) tensors of one shape, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    if img1.numel() == 0:
+        raise RuntimeError("ssim_mean: empty input")
+    C = img1.shape[1]
+    g = ssim_window_1d().to(device=img1.device, dtype=torch.float64)
+    rows, cols = g.view(1, 1, 1, 11).repeat(C, 1, 1, 1), g.view(1, 1, 11, 1).repeat(C, 1, 1, 1)
+
+    def blur(t):
+        return F.conv2d(F.conv2d(t, rows, padding=(0, 5), groups=C), cols, padding=(5, 0), groups=C)
+    a, b = img1.double(), img2.double()
+    mu1, mu2 = blur(a), blur(b)
+    s1, s2, s12 = blur(a * a) - mu1 * mu1, blur(b * b) - mu2 * mu2, blur(a * b) - mu1 * mu2
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    s_map = ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2))
+    return s_map.mean().to(img1.dtype)

@@ -89,7 +89,7 @@ using namespace wm;
 
 extern "C" {
 
-int wm_abi_version(void) { return 33; }
+int wm_abi_version(void) { return 34; }
 
 #ifndef WM_BUILD_ID
 #define WM_BUILD_ID "unknown"

@@ -1,9 +1,11 @@
-// haar_image.hip - C ABI over the Haar transforms, uint8 image I/O, the L1 loss and the image-quality metrics.
+// haar_image.hip - C ABI over the Haar transforms, uint8 image I/O, the L1 and SSIM losses and the image-quality metrics.
+#include <initializer_list>
 #include "host_common.h"
 #include "haar.hip.h"
 #include "imageio.hip.h"
 #include "loss.hip.h"
 #include "metrics.hip.h"
+#include "ssim_loss.hip.h"
 
 namespace wm {
 
@@ -75,6 +77,45 @@ static bool met_window(int N, int H, int W, int crop, int& Hc, int& Wc) {
     Hc = H - 2 * crop;
     Wc = W - 2 * crop;
     return Hc >= 1 && Wc >= 1;                         // crop >= min(H, W) / 2 leaves nothing to measure
+}
+
+// ================================================================================================
+// SSIM training loss (csrc/ssim_loss.hip.h)
+// ================================================================================================
+// The 1-D window exactly as cal_ssim.py:7-9 has it: exp(-(i - 5)^2 / 4.5) evaluated and normalised in float32 by torch
+// (taps 0..5; the window is symmetric).  Constants, not arithmetic: the float32 sum these were divided by depends on torch's
+// summation order (a sequential sum differs in the last bit), and a last bit of the window's sum is 1e-4 of B2 on a flat
+// bright region (see the header of ssim_loss.hip.h).  tests/test_ssim_loss_cpu.py holds cpu_twin.ssim_window_1d() to them.
+static const float SL_TAPS_F32[6] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f};
+
+static SlGauss sl_window() {
+    SlGauss gw;
+    for (int i = 0; i < SL_TAPS; ++i) gw.g[i] = (double)SL_TAPS_F32[i <= 5 ? i : SL_TAPS - 1 - i];
+    return gw;
+}
+
+// tiles of every plane folded into grid.x (any plane count); WM_EINVAL for an empty shape, WM_EUNSUPPORTED when the grid would
+// not fit: a launch holds fewer than 2^32 threads in all, 2^24 - 1 workgroups of 256 (SL_MAX_TILES; 12.9e9 pixels)
+static const long long SL_MAX_TILES = (1LL << 24) - 1;
+
+static int sl_geom(int64_t planes, int H, int W, SlGeom& gm, long long& blocks) {
+    if (planes < 1 || H < 1 || W < 1) return WM_EINVAL;
+    gm.H = H; gm.W = W;
+    gm.tilesX = (W + SL_TW - 1) / SL_TW;
+    gm.tilesY = (H + SL_TH - 1) / SL_TH;
+    const long long per_plane = (long long)gm.tilesX * gm.tilesY;
+    if (per_plane > SL_MAX_TILES || planes > SL_MAX_TILES / per_plane) return WM_EUNSUPPORTED;
+    blocks = (long long)planes * per_plane;
+    gm.vec = 0;
+    return WM_OK;
+}
+
+// 16-byte staging loads: W a multiple of 4 (then so is every row's and plane's offset) and each staged base 16-byte aligned
+static int sl_vec(int W, std::initializer_list<const float*> staged) {
+    if (W % 4 != 0) return 0;
+    for (const float* p : staged)
+        if (reinterpret_cast<uintptr_t>(p) & 15u) return 0;
+    return 1;
 }
 
 extern "C" {
@@ -200,6 +241,48 @@ int wm_l1_mean_bwd(const float* a, const float* b, const float* gout, float* ga,
     return launch_status();
 }
 
+size_t wm_ssim_workspace_bytes(int64_t planes, int H, int W) {
+    SlGeom gm;
+    long long blocks;
+    if (sl_geom(planes, H, W, gm, blocks) != WM_OK) return 0;
+    return (size_t)blocks * sizeof(double);
+}
+
+int wm_ssim_mean_fwd(const float* a, const float* b, float* out, float* p1, float* p2, float* q, float* r, void* workspace,
+                     size_t workspace_bytes, int64_t planes, int H, int W, void* stream) {
+    SlGeom gm;
+    long long blocks;
+    const int rc = sl_geom(planes, H, W, gm, blocks);
+    if (rc) return rc;
+    if (!a || !b || !out || !workspace) return WM_ENULL;
+    if ((q == nullptr) != (r == nullptr) || ((p1 || p2) && !q)) return WM_ENULL;      // q and r come together, with p1 and / or p2
+    if (q && !p1 && !p2) return WM_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return WM_EALIGN;
+    if (workspace_bytes < (size_t)blocks * sizeof(double)) return WM_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    gm.vec = sl_vec(W, {a, b});
+    hipLaunchKernelGGL(ssim_loss_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, gm, sl_window(), p1, p2, q, r, part);
+    const int rc2 = launch_status();
+    if (rc2) return rc2;
+    const double n = (double)planes * (double)H * (double)W;
+    hipLaunchKernelGGL(ssim_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)part, blocks, n, out);
+    return launch_status();
+}
+
+int wm_ssim_mean_bwd(const float* x, const float* other, const float* p, const float* q, const float* r, const float* gout,
+                     float* gx, int64_t planes, int H, int W, void* stream) {
+    SlGeom gm;
+    long long blocks;
+    const int rc = sl_geom(planes, H, W, gm, blocks);
+    if (rc) return rc;
+    if (!x || !other || !p || !q || !r || !gout || !gx) return WM_ENULL;
+    const double n = (double)planes * (double)H * (double)W;
+    gm.vec = sl_vec(W, {p, q, r});
+    hipLaunchKernelGGL(ssim_loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, other, p, q, r, gout, gx,
+                       gm, sl_window(), 1.0 / n);
+    return launch_status();
+}
 
 size_t wm_psnr_ssim_y_workspace_bytes(int N, int H, int W, int crop) {
     int Hc, Wc;

@@ -1395,6 +1395,69 @@ def l1_mean(a, b):
     return _L1Mean.apply(a.contiguous().float(), b.contiguous().float())
 
 
+SSIM_TILE_H, SSIM_TILE_W = 24, 32          # csrc/ssim_loss.hip.h: SL_TH x SL_TW, one workgroup per tile (the tests' edge shapes)
+
+
+def _ssim_forward(a, b, want_a, want_b):
+    """wm_ssim_mean_fwd on dense fp32 (B, C, H, W): (ssim 0-dim, p1, p2, q, r) - the derivative maps only where wanted."""
+    B, C, H, W = a.shape
+    lib = _lib.load()
+    ws_bytes = lib.wm_ssim_workspace_bytes(B * C, H, W)
+    if ws_bytes == 0:
+        raise RuntimeError(f"ssim_mean: {B * C} planes of {H} x {W} are more tiles than one launch holds (2^24 - 1)")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    p1 = torch.empty_like(a) if want_a else None
+    p2 = torch.empty_like(a) if want_b else None
+    q, r = (torch.empty_like(a), torch.empty_like(a)) if want_a or want_b else (None, None)
+    _launch(a.device, "wm_ssim_mean_fwd", a, b, out, p1, p2, q, r, ws, ws_bytes, B * C, H, W)
+    return out.reshape(()), p1, p2, q, r
+
+
+def _ssim_backward(x, other, p, q, r, g):
+    B, C, H, W = x.shape
+    gx = torch.empty_like(x)
+    _launch(x.device, "wm_ssim_mean_bwd", x, other, p, q, r, g, gx, B * C, H, W)
+    return gx
+
+
+class _SSIMMean(torch.autograd.Function):
+    """The mean SSIM of cal_ssim.py's SSIM() (femasr_model.py:29, :172) of two dense fp32 (B, C, H, W) tensors on the HIP kernels
+    of ssim_loss.hip.h.  Forward: the tile kernel and the fixed-order sum (no ATen reduction: its semaphore memset must not be
+    captured, see _L1Mean); where a gradient is wanted (want_a / want_b, decided by ssim_mean() - grad mode is off in here) the
+    same pass stores dS/dmu, dS/de11, dS/de12, and backward is one filter kernel per gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, want_a, want_b):
+        out, p1, p2, q, r = _ssim_forward(a, b, want_a, want_b)
+        ctx.want = (want_a, want_b)
+        ctx.save_for_backward(a, b, p1, p2, q, r)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, p1, p2, q, r = ctx.saved_tensors
+        g = g.contiguous().float()
+        ga = _ssim_backward(a, b, p1, q, r, g) if ctx.want[0] and ctx.needs_input_grad[0] else None
+        gb = _ssim_backward(b, a, p2, q, r, g) if ctx.want[1] and ctx.needs_input_grad[1] else None
+        return ga, gb, None, None
+
+
+def ssim_mean(img1, img2):
+    """cal_ssim.SSIM()(img1, img2) (window 11, size_average) for CUDA tensors (B, C, H, W) of one shape: a 0-dim fp32 tensor,
+    differentiable in both arguments.  The training loss is 1 - this (trainer.ssim_loss)."""
+    _require_cuda("ssim_mean", img1, img2)
+    if img1.dim() != 4 or img2.dim() != 4:
+        raise RuntimeError(f"ssim_mean: expected (B, C, H, W) tensors, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    if img1.shape != img2.shape:
+        raise RuntimeError(f"ssim_mean: shapes differ: {tuple(img1.shape)} vs {tuple(img2.shape)}")
+    if img1.numel() == 0:
+        raise RuntimeError("ssim_mean: empty input")
+    grad = torch.is_grad_enabled()
+    return _SSIMMean.apply(img1.contiguous().float(), img2.contiguous().float(), grad and img1.requires_grad,
+                           grad and img2.requires_grad)
+
+
 class _Conv2dTrain(torch.autograd.Function):
     """Dense 3x3 / 1x1 convolution (stride 1, 'same' padding) for training: forward and input gradient on the
     matrix-core kernels (the input gradient is the same convolution with the weight transposed and flipped) - the fp16 form

@@ -1,13 +1,14 @@
 """The hot-path operators as torch.library custom ops (namespace `wavemamba_hip`), for hosts that bind operators by name -
 torch.compile / torch.export graphs, C++ frontends, other packages - instead of importing `wave_mamba_amd.ops`
 ("torch.library custom ops with registered backward named wavemamba_hip::{dwt2d, idwt2d, selective_scan,
-ss2d_core}").
+ss2d_core}"), and the SSIM training loss beside them.
 
     import wave_mamba_amd.torch_ops            # registers the ops (idempotent)
     ll, hl, lh, hh = torch.ops.wavemamba_hip.dwt2d(x)                       # dwt_init          (wavemamba_arch.py:97-110)
     y = torch.ops.wavemamba_hip.idwt2d(torch.cat([ll, hl, lh, hh], 1))     # iwt_init          (:113-130)
     out = torch.ops.wavemamba_hip.selective_scan(u, delta, A, B, C, D, delta_bias, True)   # selective_scan_fn (:465-471)
     y0, y1, y2, y3 = torch.ops.wavemamba_hip.ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)  # (:446-478)
+    s = torch.ops.wavemamba_hip.ssim_mean(pred, gt)                        # SSIM()           (basicsr/models/cal_ssim.py:39-64)
 
 Every op is a thin shell over the C ABI calls `ops.py` makes (same kernels, same checks) under the CUDA dispatch key, has a
 fake (meta) implementation so that tracing never launches anything, and an autograd formula whose backward is itself a
@@ -141,6 +142,39 @@ def _ss2d_core_backward_fake(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A
     return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds))
 
 
+# ---- SSIM training loss -------------------------------------------------------------------------------------------------
+def _ssim_check(img1, img2):
+    torch._check(img1.dim() == 4 and img1.shape == img2.shape,
+                 lambda: f"ssim_mean: expected two (B, C, H, W) tensors of one shape, got {tuple(img1.shape)} and {tuple(img2.shape)}")
+    torch._check(img1.numel() > 0, lambda: "ssim_mean: empty input")
+
+
+def _ssim_mean(img1, img2):
+    _ssim_check(img1, img2)
+    return ops._ssim_forward(img1.detach().contiguous().float(), img2.detach().contiguous().float(), False, False)[0]
+
+
+def _ssim_mean_fake(img1, img2):
+    _ssim_check(img1, img2)
+    return img1.new_empty((), dtype=torch.float32)
+
+
+def _ssim_mean_backward(img1, img2, gout, need1, need2):
+    """The op's forward keeps no derivative maps (its outputs are the value alone), so they are made here: one more tile pass
+    than ops.ssim_mean's backward, then the same gradient kernels - the same bits."""
+    a, b = img1.detach().contiguous().float(), img2.detach().contiguous().float()
+    _, p1, p2, q, r = ops._ssim_forward(a, b, need1, need2)
+    g = gout.contiguous().float()
+    z = a.new_zeros((0,))
+    return (ops._ssim_backward(a, b, p1, q, r, g) if need1 else z), (ops._ssim_backward(b, a, p2, q, r, g) if need2 else z)
+
+
+def _ssim_mean_backward_fake(img1, img2, gout, need1, need2):
+    z = img1.new_empty((0,), dtype=torch.float32)
+    f = lambda t: t.new_empty(t.shape, dtype=torch.float32)
+    return (f(img1) if need1 else z), (f(img2) if need2 else z)
+
+
 _define("dwt2d", "(Tensor x) -> (Tensor, Tensor, Tensor, Tensor)", _dwt2d, _dwt2d_fake)
 _define("dwt2d_backward", "(Tensor g_ll, Tensor g_hl, Tensor g_lh, Tensor g_hh) -> Tensor", _dwt2d_backward, _dwt2d_backward_fake)
 _define("idwt2d", "(Tensor x) -> Tensor", _idwt2d, _idwt2d_fake)
@@ -155,6 +189,9 @@ _define("ss2d_core", "(Tensor x, Tensor x_proj_weight, Tensor dt_projs_weight, T
 _define("ss2d_core_backward", "(Tensor x, Tensor x_proj_weight, Tensor dt_projs_weight, Tensor dt_projs_bias, Tensor A_logs, "
         "Tensor Ds, Tensor dy0, Tensor dy1, Tensor dy2, Tensor dy3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
         _ss2d_core_backward, _ss2d_core_backward_fake)
+_define("ssim_mean", "(Tensor img1, Tensor img2) -> Tensor", _ssim_mean, _ssim_mean_fake)
+_define("ssim_mean_backward", "(Tensor img1, Tensor img2, Tensor gout, bool need1, bool need2) -> (Tensor, Tensor)",
+        _ssim_mean_backward, _ssim_mean_backward_fake)
 
 
 
@@ -198,6 +235,17 @@ _cpu("selective_scan_backward", _selective_scan_backward_cpu)
 _cpu("ss2d_core", lambda x, Wx, Wdt, bias, A_logs, Ds: tuple(t.contiguous() for t in cpu_twin.ss2d_core(x, Wx, Wdt, bias, A_logs, Ds)))
 _cpu("ss2d_core_backward", lambda x, Wx, Wdt, bias, A_logs, Ds, dy0, dy1, dy2, dy3: tuple(
     g.float() for g in _twin_vjp(cpu_twin.ss2d_core, [x, Wx, Wdt, bias, A_logs, Ds], [dy0, dy1, dy2, dy3])))
+
+_cpu("ssim_mean", lambda img1, img2: cpu_twin.ssim_mean(img1, img2).float())
+
+
+def _ssim_mean_backward_cpu(img1, img2, gout, need1, need2):
+    ga, gb = _twin_vjp(cpu_twin.ssim_mean, [img1, img2], [gout.to(img1.dtype)])
+    z = img1.new_zeros((0,), dtype=torch.float32)
+    return (ga.float() if need1 else z), (gb.float() if need2 else z)
+
+
+_cpu("ssim_mean_backward", _ssim_mean_backward_cpu)
 
 _o = torch.ops.wavemamba_hip
 
@@ -258,5 +306,18 @@ def _core_backward(ctx, g0, g1, g2, g3):
 
 torch.library.register_autograd(f"{_NS}::ss2d_core", _core_backward, setup_context=_core_setup, lib=_lib_def)
 
+def _ssim_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _ssim_autograd(ctx, g):
+    img1, img2 = ctx.saved_tensors
+    need1, need2 = ctx.needs_input_grad
+    g1, g2 = _o.ssim_mean_backward(img1, img2, g.contiguous(), need1, need2)
+    return (g1.to(img1.dtype) if need1 else None), (g2.to(img2.dtype) if need2 else None)
+
+
+torch.library.register_autograd(f"{_NS}::ssim_mean", _ssim_autograd, setup_context=_ssim_setup, lib=_lib_def)
+
 OPS = ("dwt2d", "dwt2d_backward", "idwt2d", "idwt2d_backward", "selective_scan", "selective_scan_backward", "ss2d_core",
-       "ss2d_core_backward")
+       "ss2d_core_backward", "ssim_mean", "ssim_mean_backward")

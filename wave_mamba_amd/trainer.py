@@ -3,7 +3,8 @@
 Reproduces exactly what `FeMaSRModel.optimize_parameters` (:157-185) does to the network:
     loss = L1(output, gt) + 0.1 * L1(stack(rfft2(output).real/imag), stack(rfft2(gt).real/imag))
 (`self.l1` is a bare nn.L1Loss :30,:171; FFTLoss losses.py:306-313 with fft_opt.loss_weight 0.1,
-train_wavemamba_uhdll.yml:102-104), AdamW(lr 5e-4, weight_decay 1e-3, betas (0.9, 0.99)) (yml:75-79),
+train_wavemamba_uhdll.yml:102-104; with `ssim_weight` the recipe's third term, ssim_weight * (1 - SSIM()(output, gt)),
+cal_ssim.py / femasr_model.py:29, :172 / yml:99-100, joins the sum), AdamW(lr 5e-4, weight_decay 1e-3, betas (0.9, 0.99)) (yml:75-79),
 DistributedDataParallel wrap with one gradient all-reduce per step (base_model.py:111-114; backend
 'nccl' == RCCL on ROCm), and the per-iteration loss reduce to rank 0 (base_model.py:376-401).
 """
@@ -34,8 +35,34 @@ def fft_l1(pred, target):
     return F.l1_loss(torch.stack([pf.real, pf.imag], dim=-1), torch.stack([tf.real, tf.imag], dim=-1))
 
 
-def losses(output, gt, fft_weight=0.1):
-    return l1(output, gt), fft_weight * fft_l1(output, gt)
+def ssim_loss(pred, target):
+    """1 - SSIM()(pred, target): the recipe's SSIM term (self.ssim = SSIM().cuda(), femasr_model.py:29, its use at :172;
+    cal_ssim.py:39-64; pixel_ssim_opt, train_wavemamba_uhdll.yml:99-100).  GPU fp32 tensors: the fused HIP forward / backward
+    (ops.ssim_mean) - two launches and one per gradient, no ATen reduction, capturable like l1.  Anything else (CPU tensors, other
+    dtypes): the plain-PyTorch statement of the same definition (cpu_twin.ssim_mean)."""
+    if _on_hip(pred, target):
+        from . import ops
+        return 1 - ops.ssim_mean(pred, target)
+    from . import cpu_twin
+    return 1 - cpu_twin.ssim_mean(pred, target)
+
+
+def losses(output, gt, fft_weight=0.1, ssim_weight=None):
+    """(l_pix, l_freq), and with an `ssim_weight` (the recipe's is 0.25) a third term ssim_weight * ssim_loss."""
+    if ssim_weight is None:
+        return l1(output, gt), fft_weight * fft_l1(output, gt)
+    return l1(output, gt), fft_weight * fft_l1(output, gt), ssim_weight * ssim_loss(output, gt)
+
+
+_LOSS_NAMES = ("l_pix", "l_freq", "l_ssim")
+
+
+def _total(terms):
+    """The scalar that is differentiated: l_pix + l_freq, plus the weighted SSIM term where there is one."""
+    total = terms[0] + terms[1]
+    for t in terms[2:]:
+        total = total + t
+    return total.mean()
 
 
 def make_optimizer(net, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.99), capturable=False):
@@ -67,8 +94,9 @@ def wrap_ddp(net, device=None, find_unused_parameters=False, force=False):
                                                      find_unused_parameters=find_unused_parameters)
 
 
-def train_step(net, optimizer, lq, gt, as_float=True):
-    """One optimize_parameters(): zero_grad, forward, L1 + 0.1*FFT, backward (DDP all-reduce), step.
+def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None):
+    """One optimize_parameters(): zero_grad, forward, L1 + 0.1*FFT (+ ssim_weight * (1 - SSIM) where a weight is given; the
+    loss dict then has "l_ssim", weighted like l_freq), backward (DDP all-reduce), step.
     Returns the reduced losses {name: python float} like the reference's `reduce_loss_dict` (base_model.py:376-401: a log dict
     of floats - callers format / json-dump it).  as_float=False returns 0-dim DEVICE tensors instead: nothing in the step then
     waits for the GPU (a `float()` is a host synchronisation per iteration, under DDP on every rank); `loss_values()` converts
@@ -76,10 +104,10 @@ def train_step(net, optimizer, lq, gt, as_float=True):
     step with as_float=False."""
     optimizer.zero_grad(set_to_none=True)
     out = net(lq)
-    l_pix, l_freq = losses(out, gt)
-    (l_pix + l_freq).mean().backward()
+    terms = losses(out, gt, ssim_weight=ssim_weight)
+    _total(terms).backward()
     optimizer.step()
-    return reduce_loss_dict({"l_pix": l_pix.detach(), "l_freq": l_freq.detach()}, as_float=as_float)
+    return reduce_loss_dict({k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}, as_float=as_float)
 
 
 class GraphedTrainStep:
@@ -93,9 +121,10 @@ class GraphedTrainStep:
 
         step = GraphedTrainStep(net, optimizer, lq0, gt0)          # 3 eager warm-up steps on (lq0, gt0), then the capture
         losses = step(lq, gt)                                      # copies the batch into the graph's input buffers, replays
-    Returns {"l_pix", "l_freq"} as 0-dim device tensors of the step just replayed (loss_values() to log them)."""
+    Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`) as 0-dim device tensors of the step just replayed
+    (loss_values() to log them)."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep: single-process training only (under torch.distributed: GraphedDDPTrainStep)")
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
@@ -108,7 +137,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(lq.device))
         with torch.cuda.stream(side):                              # warm-up off the capture's stream (allocator pools, library set-up)
             for _ in range(warmup):
-                train_step(net, optimizer, self.lq, self.gt, as_float=False)
+                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight)
         torch.cuda.current_stream(lq.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -120,10 +149,10 @@ class GraphedTrainStep:
             mode = {"capture_error_mode": "thread_local"}
         with torch.cuda.graph(self.graph, **mode):
             out = net(self.lq)
-            l_pix, l_freq = losses(out, self.gt)
-            (l_pix + l_freq).mean().backward()
+            terms = losses(out, self.gt, ssim_weight=ssim_weight)
+            _total(terms).backward()
             optimizer.step()
-        self.losses = {"l_pix": l_pix.detach(), "l_freq": l_freq.detach()}
+        self.losses = {k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}
 
     def __call__(self, lq=None, gt=None):
         if lq is not None:
@@ -139,7 +168,7 @@ class GraphedDDPTrainStep:
     base_model.py:111-114) with the host taken out of the step: every rank replays
 
         graph A   forward, both losses, backward, the 591 gradients (pre-divided by the world size, as DDP's reducer does)
-                  and the two losses copied into ONE flat fp32 buffer
+                  and the two losses (three with an `ssim_weight`) copied into ONE flat fp32 buffer
         exchange  ONE all-reduce (sum) of that buffer - RCCL over xGMI: 6.05 MB per step for the shipped config
         graph B   AdamW on gradients that ARE views of the buffer
 
@@ -151,11 +180,12 @@ class GraphedDDPTrainStep:
         "captured"  one graph holds A, the all-reduce and B (backend nccl = RCCL only: its collectives are stream-ordered
                     kernels and capture like any other launch)
     `capture=False` runs the same three phases eagerly - what the CPU / gloo tests exercise, and the cross-check of the replays.
-    Fixed batch shape; `optimizer` as for GraphedTrainStep on a GPU.  Returns {"l_pix", "l_freq"}: 0-dim tensors holding the
+    Fixed batch shape; `optimizer` as for GraphedTrainStep on a GPU.  `ssim_weight`: the weighted SSIM term joins the sum and
+    rides in the buffer as a third loss.  Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`): 0-dim tensors holding the
     MEAN over ranks of the step just run (every rank has them - they ride in the gradient buffer; the reference's
     reduce_loss_dict, base_model.py:376-401, leaves them on rank 0 only)."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split"):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split", ssim_weight=None):
         if isinstance(net, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)):
             raise RuntimeError("GraphedDDPTrainStep: pass the bare module, not its DistributedDataParallel wrap")
         if not (dist.is_available() and dist.is_initialized()):
@@ -165,6 +195,7 @@ class GraphedDDPTrainStep:
         self.group = process_group
         self.world = dist.get_world_size(process_group)
         self.net, self.optimizer, self.capture, self.collective = net, optimizer, capture, collective
+        self.ssim_weight = ssim_weight
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         if capture:
             if not all(p.is_cuda for p in self.params):
@@ -181,9 +212,10 @@ class GraphedDDPTrainStep:
                                group=process_group)
         dev = self.params[0].device
         self.sizes = [p.numel() for p in self.params]
-        self.flat = torch.zeros(sum(self.sizes) + 2, dtype=torch.float32, device=dev)     # gradients | l_pix | l_freq
-        self.views = [v.view_as(p) for v, p in zip(self.flat[:-2].split(self.sizes), self.params)]
-        self.losses = {"l_pix": self.flat[-2], "l_freq": self.flat[-1]}
+        nl = 2 if ssim_weight is None else 3
+        self.flat = torch.zeros(sum(self.sizes) + nl, dtype=torch.float32, device=dev)    # gradients | l_pix | l_freq (| l_ssim)
+        self.views = [v.view_as(p) for v, p in zip(self.flat[:-nl].split(self.sizes), self.params)]
+        self.losses = {k: self.flat[i - nl] for i, k in enumerate(_LOSS_NAMES[:nl])}
         self.lq, self.gt = lq.clone(), gt.clone()
         if not capture:
             return
@@ -217,12 +249,12 @@ class GraphedDDPTrainStep:
         for p in self.params:
             p.grad = None
         out = self.net(self.lq)
-        l_pix, l_freq = losses(out, self.gt)
-        (l_pix + l_freq).mean().backward()
+        terms = losses(out, self.gt, ssim_weight=self.ssim_weight)
+        _total(terms).backward()
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in self.params]
         torch._foreach_copy_(self.views, grads)
-        self.flat[-2].copy_(l_pix.detach())
-        self.flat[-1].copy_(l_freq.detach())
+        for k, t in zip(_LOSS_NAMES, terms):
+            self.losses[k].copy_(t.detach())
         self.flat.mul_(1.0 / self.world)                           # DDP's reducer divides before it sums
 
     def _exchange(self):
