@@ -287,6 +287,17 @@ int wm_conv2d_prep(const float* weight, void* wfrag, int Cout, int Cin, int ks, 
  * wm_conv2d_prep(weight (Cout, 32, 1, 1)); bias, residual may be NULL. */
 int wm_conv2d_ln_fwd(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* wfrag, const float* bias,
                      const float* residual, float* y, int B, int Cin, int Cout, int H, int W, void* stream);
+/* y = conv1x1(act(dwconv3x3(x) + dw_bias)) + bias (+ residual): a depth-wise 3x3 whose only reader is a 1x1 convolution, as ONE
+ * kernel - FeedForward.project_out (wavemamba_arch.py:739-741, act = GELU) and the value third of CMTAttention.qkv_dwconv under the
+ * folded project_out (:771, :797).  Bit-identical to wm_dwconv3x3_fwd + wm_conv2d_fwd; the plane between them (256 B per position,
+ * written and read back) never exists.  x: 32 consecutive channel planes (H, W) fp32 per batch element, batch elements
+ * x_batch_stride ELEMENTS apart (a channel slice of a wider tensor; 4-byte alignment suffices); dw_weight (32, 1, 3, 3); dw_bias (32)
+ * or NULL; act: 0 = none, 2 = GELU (exact erf form), anything else WM_EINVAL; `wfrag` from wm_conv2d_prep(weight (32, 32, 1, 1));
+ * bias, residual (B, 32, H, W) may be NULL; y (B, 32, H, W) aliases no input.  C == Cout == 32 and H W < 2^26 only
+ * (WM_EUNSUPPORTED otherwise: use the two calls). */
+int wm_dwconv_conv1x1_fwd(const float* x, int64_t x_batch_stride, const float* dw_weight, const float* dw_bias, int act,
+                          const void* wfrag, const float* bias, const float* residual, float* y, int B, int C, int Cout, int H,
+                          int W, void* stream);
 /* The training form of the same convolutions (the F.conv2d calls of wavemamba_arch.py under autograd, femasr_model.py:170-181:
  * forward, and - on the transposed, flipped weight - the input gradient): fp16 matrix cores, two-term split of both operands
  * (22 significant bits, fp32-class: ~1e-7 relative to an fp64 convolution instead of the bf16 form's 3-4e-6, which the

@@ -145,6 +145,16 @@ def _ln_conv(norm, conv, x):
     return _conv(conv, norm(x))
 
 
+def _dw_pw_fused(x, dw_weight, pw_weight):
+    """A depth-wise 3x3 (weight `dw_weight`, input `x`) whose output only the 1x1 convolution `pw_weight` reads runs as ONE kernel
+    (ops.dwconv_conv1x1: the plane between them never reaches HBM, bit-identical to the two launches): the backend has it, covers
+    the operands, and the map is one the HIP library's size rule sends there (ops._fuse_dw_pw_map: measured per UHD level; smaller
+    maps keep the pair).  The caller adds `_needs_grad`: forward only."""
+    ops = _OpsBackend.impl
+    return bool(_op("dwconv_conv1x1") and ops.dwconv_conv1x1_supported(x, dw_weight, pw_weight)
+                and _hip_ops._fuse_dw_pw_map(x.shape[0], x.shape[2], x.shape[3]))
+
+
 def _cat_gathered(x, x2=None, x2_index=None):
     """cat([x, gather(x2, 1, x2_index)], 1) (x2_index None: cat([x, x2], 1); x2 None: x)."""
     if x2 is None:
@@ -536,8 +546,12 @@ class FeedForward(nn.Module):
         y = _dwconv(self.project_in[1], _ln_conv(norm, self.project_in[0], x))
         if perception is not None:
             y = self.matching_transformation(y, perception)
-        # project_out = [depth-wise 3x3, GELU, 1x1]: the GELU rides in the depth-wise kernel
-        return _conv(self.project_out[2], _dwconv(self.project_out[0], y, act="gelu"), residual=residual)
+        dw, pw = self.project_out[0], self.project_out[2]
+        if _dw_pw_fused(y, dw.weight, pw.weight) and not _needs_grad(dw, y, residual) and not _needs_grad(pw):
+            # project_out = [depth-wise 3x3, GELU, 1x1] (+ the block's residual) in one kernel
+            return _OpsBackend.impl.dwconv_conv1x1(y, dw.weight, dw.bias, "gelu", pw.weight, pw.bias, residual=residual)
+        # the pair: the GELU rides in the depth-wise kernel
+        return _conv(pw, _dwconv(dw, y, act="gelu"), residual=residual)
 
 
 class CMTAttention(nn.Module):
@@ -559,19 +573,38 @@ class CMTAttention(nn.Module):
 
     def qkv_of(self, x, norm=None):
         """The part of `forward` that needs `x` alone (UNet.forward runs it ahead of time on a side stream).  `norm`: the
-        block's norm1, applied to `x` here (it rides in the qkv 1x1 kernel)."""
-        return _dwconv(self.qkv_dwconv, _ln_conv(norm, self.qkv, x))
+        block's norm1, applied to `x` here (it rides in the qkv 1x1 kernel).  Returns dwconv(qkv(norm(x))) - or, where the value
+        third's depth-wise conv can ride in the folded project_out (inference, batch 1: the q | k channels of one image are
+        contiguous), the pair (dwconv of the q | k channels, qkv(norm(x)) itself): `forward` takes both forms."""
+        pre = _ln_conv(norm, self.qkv, x)
+        dw = self.qkv_dwconv
+        c = pre.shape[1] // 3
+        ops = _OpsBackend.impl
+        if (pre.shape[0] == 1 and _op("attn_fold") and _op("dwconv3x3") and ops.dwconv3x3_supported(pre)
+                and _dw_pw_fused(pre[:, 2 * c:], dw.weight[2 * c:], self.project_out.weight) and not _needs_grad(self, pre)):
+            return ops.dwconv3x3(pre[:, :2 * c], dw.weight[:2 * c], None if dw.bias is None else dw.bias[:2 * c]), pre
+        return _dwconv(dw, pre)
 
     def forward(self, x, perception, residual=None, qkv=None, norm=None):
-        q, k, v = (self.qkv_of(x, norm) if qkv is None else qkv).chunk(3, dim=1)
-        x = v                                              # from here on only shape / device / dtype of `x` matter
+        qkv = self.qkv_of(x, norm) if qkv is None else qkv
+        pre = None
+        if isinstance(qkv, tuple):                         # (dwconv of q | k, the qkv 1x1's output): v's depth-wise conv is still to come
+            qk, pre = qkv
+            (q, k), v = qk.chunk(2, dim=1), None
+        else:
+            q, k, v = qkv.chunk(3, dim=1)
+        x = k                                              # from here on only shape / device / dtype of `x` matter
         b, c, h, w = x.shape
+        dw = self.qkv_dwconv
+        dw_v = (dw.weight[2 * c:], None if dw.bias is None else dw.bias[2 * c:])      # the value third of the depth-wise conv
+
+        def value():                                       # v; where the fold was not taken after all, a plain depth-wise conv of the slice
+            return v if pre is None else _OpsBackend.impl.dwconv3x3(pre[:, 2 * c:], *dw_v)
         if self.matching is True:
             q = self.matching_transformation(q, perception)
         heads = self.num_heads
         q = q.reshape(b * heads, c // heads, h * w)
         k = k.reshape(b * heads, c // heads, h * w)
-        v = v.reshape(b, heads, c // heads, h * w)
         ops = _OpsBackend.impl
         train_gram = _needs_grad(None, q, k)               # the Gram matrix under autograd: gram_train, where the backend has it
         if _op("gram") and ops.gram_supported(q, k) and (not train_gram or _op("gram_train")):
@@ -584,8 +617,10 @@ class CMTAttention(nn.Module):
                 # project_out(softmax(...) @ v) = (W_po @ blockdiag(attn)) @ v: a tiny kernel folds the (c/heads)^2
                 # attention into the 1x1 weight, the 1x1 convolution kernel applies it (+ bias, + residual)
                 wf = ops.attn_fold(G, nq, nk, self.temperature.reshape(heads), self.project_out.weight, b, heads)
-                vv = v.reshape(b, c, h, w)
-                outs = [ops.conv2d(vv[i:i + 1], wf[i].view(c, c, 1, 1), self.project_out.bias,
+                if pre is not None:                        # batch 1: v = dwconv(pre[:, 2c:]) inside the folded 1x1's kernel
+                    return ops.dwconv_conv1x1(pre[:, 2 * c:], *dw_v, "none", wf[0].view(c, c, 1, 1), self.project_out.bias,
+                                              residual=residual, dynamic_weight=True)
+                outs = [ops.conv2d(v[i:i + 1], wf[i].view(c, c, 1, 1), self.project_out.bias,
                                    residual=None if residual is None else residual[i:i + 1], dynamic_weight=True)
                         for i in range(b)]
                 return outs[0] if b == 1 else torch.cat(outs, 0)
@@ -598,7 +633,7 @@ class CMTAttention(nn.Module):
             kn = F.normalize(k.reshape(b, heads, c // heads, h * w), dim=-1)
             attn = qn @ kn.transpose(-2, -1)
         attn = (attn * self.temperature).softmax(dim=-1)
-        return _conv(self.project_out, (attn @ v).reshape(b, c, h, w), residual=residual)
+        return _conv(self.project_out, (attn @ value().reshape(b, heads, c // heads, h * w)).reshape(b, c, h, w), residual=residual)
 
 
 class HFEBlock(nn.Module):
@@ -721,6 +756,8 @@ class DownFRG(nn.Module):
             high = self.h_fusion([hl, lh, hh])
             # the part of the first HFEBlock that needs `high` alone (norm1 -> qkv 1x1 -> depth-wise 3x3) runs under the main
             # stream's LFSS stack too, not behind it (the up groups do the same with their branch, UNet.forward)
+            # (qkv0 - a tensor, or the (q | k, pre-depth-wise qkv) pair of CMTAttention.qkv_of - is produced and consumed on `side`:
+            # no record_stream here, unlike UNet.forward's join, which hands both tensors to the main stream)
             qkv0 = self.h_blk[0].qkv_of(high) if (len(self.h_blk) and self.early_qkv) else None
         if x_d_ready is not None:                      # x_d was computed on `side` (UNet.forward)
             main.wait_event(x_d_ready)
@@ -844,7 +881,7 @@ class UNet(nn.Module):
             def join(high):
                 main = torch.cuda.current_stream(x.device)
                 main.wait_stream(side)
-                for t in (high, qkv):                  # allocated on `side`, read on `main`
+                for t in (high, *(qkv if isinstance(qkv, tuple) else (qkv,))):   # allocated on `side`, read on `main`
                     if t is not None:
                         t.record_stream(main)
                 return high, qkv

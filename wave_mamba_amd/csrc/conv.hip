@@ -1,8 +1,10 @@
-// conv.hip - C ABI over the dense convolutions (first-generation and wave-specialised kernels) and the patchify convolution.
+// conv.hip - C ABI over the dense convolutions (first-generation and wave-specialised kernels), the patchify convolution and the
+// depth-wise 3x3 folded into a 1x1 (dw_pw.hip.h).
 #include "host_common.h"
 #include "conv2d.hip.h"
 #include "conv2d_ws.hip.h"
 #include "patchify.hip.h"
+#include "dw_pw.hip.h"
 
 using namespace wm;
 
@@ -201,6 +203,45 @@ int wm_conv2d_ln_fwd(const float* x, const float* ln_weight, const float* ln_bia
         if (rc) return rc;
     }
     return WM_OK;
+}
+
+// y = conv1x1(act(dwconv3x3(x) + dw_bias)) + bias (+ residual) in one kernel (dw_pw.hip.h): bit-identical to wm_dwconv3x3_fwd +
+// wm_conv2d_fwd, without the plane between them.
+int wm_dwconv_conv1x1_fwd(const float* x, int64_t x_batch_stride, const float* dw_weight, const float* dw_bias, int act,
+                          const void* wfrag, const float* bias, const float* residual, float* y, int B, int C, int Cout, int H,
+                          int W, void* stream) {
+    if (B < 0 || C <= 0 || Cout <= 0 || H < 0 || W < 0 || x_batch_stride < 0) return WM_EINVAL;
+    if (act != 0 && act != 2) return WM_EINVAL;
+    if (C != 32 || Cout != 32) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !dw_weight || !wfrag || !y) return WM_ENULL;
+    if ((long long)H * W >= (1ll << 26)) return WM_EUNSUPPORTED;    // 32-bit element offsets inside a batch element
+    if (B > 1 && x_batch_stride < (long long)C * H * W) return WM_EINVAL;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    DwPwArgs a;
+    a.x = x; a.xbs = x_batch_stride; a.dw_w = dw_weight; a.dw_b = dw_bias; a.wfrag = (const uint4*)wfrag; a.bias = bias;
+    a.res = residual; a.y = y; a.H = H; a.W = W;
+    a.nstrips = (W + kCvTW - 1) / kCvTW;
+    // rows per band (a band re-reads two input rows and re-forms their taps): the tallest of 16, 8, 4 that still gives every SIMD of
+    // a 256-unit chip a wave (UHD level 1: 4080 walks of 16 rows, level 2: 2040 of 8, level 3: 1020 of 4)
+    a.rows = 4;
+    for (int rows = 16; rows > 4; rows >>= 1)
+        if ((long long)B * a.nstrips * ((H + rows - 1) / rows) >= 1024) { a.rows = rows; break; }
+    a.nbands = (H + a.rows - 1) / a.rows;
+    a.nwalks = (long long)B * a.nbands * a.nstrips;
+    const long long nblocks = ((a.nwalks + 3) / 4 + 7) / 8 * 8;       // a multiple of 8: the kernel deals contiguous runs to the XCDs
+    if (nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
+    const dim3 grid((unsigned)nblocks);
+    ProfScope ps(14, st);
+    if (act == 2) {
+        if (residual) hipLaunchKernelGGL((dw_pw_kernel<true, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dw_pw_kernel<true, false>), grid, dim3(256), 0, st, a);
+    } else {
+        if (residual) hipLaunchKernelGGL((dw_pw_kernel<false, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dw_pw_kernel<false, false>), grid, dim3(256), 0, st, a);
+    }
+    return launch_status();
 }
 
 // The training form (conv2d.hip.h, fp16 split with per-tensor power-of-two scales): y = conv(x, w) + bias, ks in {1, 3}; wfrag from

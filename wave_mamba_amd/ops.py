@@ -1271,6 +1271,56 @@ def conv2d_ln(x, ln_weight, ln_bias, ln_eps, weight, bias=None, residual=None):
 _FUSE_LN_CONV = True      # False (tests / tools): LayerNorm2d and the 1x1 convolution as two launches
 
 
+# A depth-wise 3x3 whose only reader is a 1x1 convolution, as ONE kernel (wm_dwconv_conv1x1_fwd: the plane between them never
+# reaches HBM, 256 of the pair's 640 B per position; bit-identical).  False (tests / tools): the two launches.
+_FUSE_DW_PW = True
+# The maps the HFE branch sends to it: at least as many positions PER IMAGE as the smallest UHD level at which the fused call
+# measured faster than the pair - level 3, the smallest level there is: nothing below it is measured, so nothing smaller takes it -
+# and inside the entry's offset range (H W < 2^26).  Per call, pair -> fused, median of 7 x 20 calls with [slowest fused, fastest
+# pair] (tools/bench_dw_pw.py, profiles/dw_pw/per_call.txt).  ffn tail: dwconv3x3(GELU) + conv1x1(+ residual) -> the fused call;
+# value path: dwconv3x3 over 96 channels + conv1x1(v, + residual) -> dwconv3x3 over the 64 q | k channels + the fused call:
+#   UHD level 1 (1088 x 1920)  ffn 0.287 -> 0.179 ms [0.191, 0.286]   value 0.498 -> 0.397 ms [0.398, 0.498]
+#   UHD level 2 ( 544 x  960)  ffn 0.075 -> 0.043 ms [0.043, 0.074]   value 0.137 -> 0.111 ms [0.112, 0.136]
+#   UHD level 3 ( 272 x  480)  ffn 0.029 -> 0.019 ms [0.019, 0.029]   value 0.037 -> 0.029 ms [0.030, 0.037]
+_FUSE_DW_PW_MIN_POSITIONS = 272 * 480
+
+
+def _fuse_dw_pw_map(B, H, W):
+    """Maps on which the HFE branch takes dwconv_conv1x1: inside the entry's offset range and, per image, at least as large as the
+    smallest map at which it measured faster than the pair."""
+    return _FUSE_DW_PW and B > 0 and _FUSE_DW_PW_MIN_POSITIONS <= H * W < (1 << 26)
+
+
+def dwconv_conv1x1_supported(x, dw_weight, weight):
+    """Operands wm_dwconv_conv1x1_fwd covers: fp32 on the GPU, 32 -> 32 channels, a (32, 1, 3, 3) depth-wise weight."""
+    return (x.is_cuda and x.dim() == 4 and x.shape[1] == 32 and tuple(dw_weight.shape) == (32, 1, 3, 3)
+            and tuple(weight.shape) == (32, 32, 1, 1) and all(t.dtype == torch.float32 for t in (x, dw_weight, weight)))
+
+
+def dwconv_conv1x1(x, dw_weight, dw_bias, act, weight, bias=None, residual=None, dynamic_weight=False):
+    """F.conv2d(act(F.conv2d(x, dw_weight, dw_bias, padding=1, groups=32)), weight, bias) (+ residual) in one kernel
+    (wm_dwconv_conv1x1_fwd), act in ('none', 'gelu'): x (B, 32, H, W) fp32 - a channel slice of a wider contiguous tensor is read in
+    place -, dw_weight (32, 1, 3, 3), weight (32, 32, 1, 1).  Bit-identical to conv2d(dwconv3x3(x, ...), ...).  Forward only.
+    dynamic_weight: `weight` is a freshly computed tensor (no prepared-copy cache)."""
+    _require_cuda("dwconv_conv1x1", x, dw_weight, dw_bias, weight, bias, residual)
+    if not dwconv_conv1x1_supported(x, dw_weight, weight):
+        raise NotImplementedError("dwconv_conv1x1: fp32, 32 -> 32 channels, (32, 1, 3, 3) depth-wise and (32, 32, 1, 1) dense weights")
+    if act not in ("none", "gelu"):
+        raise ValueError(f"dwconv_conv1x1: act must be 'none' or 'gelu', got {act!r}")
+    B, C, H, W = x.shape
+    if residual is not None and (tuple(residual.shape) != (B, 32, H, W) or residual.dtype != torch.float32):
+        raise RuntimeError(f"dwconv_conv1x1: residual must be float32 {(B, 32, H, W)}, got {tuple(residual.shape)}")
+    if tuple(x.stride()[1:]) != (H * W, W, 1) or (B > 1 and x.stride(0) < C * H * W):
+        x = x.contiguous()                                         # planes (H, W) back to back; any batch stride beyond them
+    frag = _conv2d_wfrag(weight, cache=not dynamic_weight)
+    y = torch.empty((B, 32, H, W), dtype=torch.float32, device=x.device)
+    _launch(x.device, "wm_dwconv_conv1x1_fwd", x, x.stride(0) if B > 1 else C * H * W, _w(dw_weight),
+            None if dw_bias is None else _w(dw_bias), {"none": 0, "gelu": 2}[act], frag,
+            None if bias is None else bias.detach().contiguous(), None if residual is None else residual.contiguous(), y,
+            B, C, 32, H, W)
+    return y
+
+
 def patchify_conv_supported(img, weight, r):
     """Shapes wm_patchify_conv_fwd covers: nn.PixelUnshuffle(r) + 1x1 nn.Conv2d on an fp32 NCHW image."""
     return (img.is_cuda and img.dtype == torch.float32 and img.dim() == 4 and weight.dim() == 4 and r in (2, 4, 8)
