@@ -319,6 +319,25 @@ int wm_conv2d_fwd(const float* xa, const float* xb, const int* xb_index, const v
 int wm_conv2d_gated_fwd(const float* xa, const float* xb, const int* xb_index, const void* wfrag3, const void* wfrag1,
                         const float* bias1, float* y, int B, int Ca, int Cb, int Cb_src, int Cout, int H, int W,
                         void* stream);
+/* (ll, hl, lh, hh) = dwt_init(conv3x3(img) + bias): a 3x3 convolution whose only reader is the Haar analysis, as ONE kernel -
+ * UNet.conv_01 followed by down_group1's DWT (wavemamba_arch.py:1037, :973).  The wave-specialised kernel forms the four sub-bands
+ * of each 2x2 quad in its epilogue; the full-resolution plane between the two (written once, read once) never exists.  Bit-identical
+ * to wm_conv2d_fwd + wm_dwt2d_fwd.  img (B, Cin, H, W); `wfrag` from wm_conv2d_prep(weight (Cout, Cin, 3, 3)); bias (Cout) or NULL;
+ * ll, hl, lh, hh each (B, Cout, H / 2, W / 2).  H, W odd: WM_EINVAL.  dtype == WM_F32 and Cout == 32 only, and only where the
+ * wave-specialised kernel runs (a batch element of the input and of the plane < 4 GiB, wm_conv2d_select not 1): WM_EUNSUPPORTED
+ * otherwise (use the two calls). */
+int wm_conv2d_dwt_fwd(const void* img, const void* wfrag, const float* bias, void* ll, void* hl, void* lh, void* hh, int B, int Cin,
+                      int Cout, int H, int W, int dtype, void* stream);
+/* y = conv3x3(iwt_init(cat([low, high], 1))) + bias (+ residual): a Haar synthesis whose only reader is a 3x3 convolution, as ONE
+ * kernel - the last upFRG's IWT followed by UNet.last (wavemamba_arch.py:1006, :1062).  The producer waves of the wave-specialised
+ * kernel load the four band values of each 2x2 quad and form the input tile from them; the full-resolution plane between the two never
+ * exists.  Bit-identical to wm_idwt2d_fwd + wm_conv2d_fwd.  low (B, Cin, H / 2, W / 2) = x1, high (B, 3 Cin, H / 2, W / 2) = x2 | x3 | x4
+ * (the un-concatenated pair of wm_idwt2d_fwd); `wfrag` from wm_conv2d_prep(weight (Cout, Cin, 3, 3)); bias (Cout), residual
+ * (B, Cout, H, W) may be NULL; y (B, Cout, H, W).  H, W (of y) odd: WM_EINVAL.  dtype == WM_F32 and Cin == 32 only, and only where the
+ * wave-specialised kernel runs (a batch element of the synthesised plane and of y < 4 GiB, wm_conv2d_select not 1): WM_EUNSUPPORTED
+ * otherwise (use the two calls). */
+int wm_idwt_conv2d_fwd(const void* low, const void* high, const void* wfrag, const float* bias, const float* residual, float* y, int B,
+                       int Cin, int Cout, int H, int W, int dtype, void* stream);
 
 /* Backward of wm_ss2d_core_fwd: autograd of SS2D.forward_core (wavemamba_arch.py:446-478) - the four directional
  * flattenings, the x_proj / dt_proj einsums and the selective scan - without materialising xs / dts / Bs / Cs.

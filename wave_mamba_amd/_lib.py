@@ -83,6 +83,8 @@ SIGNATURES = {
     "wm_patchify_conv_fwd": (_i, [_p] * 4 + [_i] * 6 + [_p]),
     "wm_conv2d_f16_steps": (_i, [_p] * 6 + [_i] * 7 + [_p]),
     "wm_conv2d_gated_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p]),
+    "wm_conv2d_dwt_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p]),
+    "wm_idwt_conv2d_fwd": (_i, [_p] * 6 + [_i] * 6 + [_p]),
     "wm_conv2d_select": (_i, [_i]),
     "wm_prof_enable": (None, [ctypes.c_uint]),
     "wm_prof_collect": (_i, [_c.POINTER(_i), _c.POINTER(_c.c_double)]),

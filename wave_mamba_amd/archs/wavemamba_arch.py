@@ -155,6 +155,35 @@ def _dw_pw_fused(x, dw_weight, pw_weight):
                 and _hip_ops._fuse_dw_pw_map(x.shape[0], x.shape[2], x.shape[3]))
 
 
+def _conv_dwt_fused(conv, img):
+    """The 3x3 convolution `conv` of `img` and the Haar analysis that alone reads its output run as ONE kernel (ops.conv2d_dwt):
+    the backend has it and covers the operands, nothing wants gradients (forward only), and the image is one the HIP library's size
+    rule sends there (ops._fuse_conv_dwt_map: measured faster at 2176 x 3840 and 1088 x 1920; smaller images keep the pair)."""
+    ops = _OpsBackend.impl
+    return bool(_op("conv2d_dwt") and ops.conv2d_dwt_supported(img, conv.weight) and not _needs_grad(conv, img)
+                and _hip_ops._fuse_conv_dwt_map(img.shape[0], img.shape[2], img.shape[3]))
+
+
+def _conv_dwt(conv, img):
+    """A 3x3 nn.Conv2d whose output only a DownFRG's Haar analysis reads (UNet.conv_01 -> down_group1): the tuple of the four
+    sub-bands out of one kernel where `_conv_dwt_fused` says so (the bands are formed in the convolution's epilogue, the
+    full-resolution plane never reaches HBM, bit-identical); otherwise the convolution's output, which DownFRG.forward analyses."""
+    if _conv_dwt_fused(conv, img):
+        return _OpsBackend.impl.conv2d_dwt(img, conv.weight, conv.bias)
+    return _conv(conv, img)
+
+
+def _iwt_conv_fused(net, conv, low, out_like):
+    """The Haar synthesis at the end of the last up group and the 3x3 convolution `conv` that alone reads it (UNet.last) run as ONE
+    kernel (ops.iwt_conv2d: the convolution forms its input tile from the bands, the full-resolution plane never reaches HBM,
+    bit-identical): the backend has it and covers the operands (`low`: the up group's low-frequency input, the shape of its output),
+    nothing in `net` wants gradients (forward only), and the output (shaped like `out_like`) is one the HIP library's size rule sends
+    there (ops._fuse_iwt_conv_map: measured faster at 2176 x 3840 and 1088 x 1920; smaller images keep the pair)."""
+    ops = _OpsBackend.impl
+    return bool(_op("iwt_conv2d") and ops.iwt_conv2d_supported(low, conv.weight) and not _needs_grad(net, low, out_like)
+                and _hip_ops._fuse_iwt_conv_map(out_like.shape[0], out_like.shape[2], out_like.shape[3]))
+
+
 def _cat_gathered(x, x2=None, x2_index=None):
     """cat([x, gather(x2, 1, x2_index)], 1) (x2_index None: cat([x, x2], 1); x2 None: x)."""
     if x2 is None:
@@ -739,18 +768,19 @@ class DownFRG(nn.Module):
                                      for _ in range(n_h_blocks)])
 
     def forward(self, x, x_d, side=None, x_d_ready=None):
-        """`side`: a second CUDA stream for the high-frequency branch (UNet.forward, inference only).  The branch needs
+        """`x`: the map, or the four sub-bands of it where the caller has them already (UNet.forward: _conv_dwt).
+        `side`: a second CUDA stream for the high-frequency branch (UNet.forward, inference only).  The branch needs
         nothing but this level's sub-bands and `low`, and nothing needs it before the matching up group: issued on its
         own stream it runs under the deeper levels' kernels (whose grids - 130 k positions at level 3 - leave compute
         units idle).  Returns (low, high); with `side`, `high` is complete on `side` (the caller joins)."""
-        ll, hl, lh, hh = self.dwt(x)
+        ll, hl, lh, hh = x if isinstance(x, tuple) else self.dwt(x)
         if side is None:
             low = _run_lfss_stack(self.l_blk, _conv(self.l_conv, ll, x_d))
             high = self.h_fusion([hl, lh, hh])
             for blk in self.h_blk:
                 high = blk(high, low)
             return low, high
-        main = torch.cuda.current_stream(x.device)
+        main = torch.cuda.current_stream(ll.device)
         side.wait_stream(main)                         # the sub-bands are ready
         with torch.cuda.stream(side):
             high = self.h_fusion([hl, lh, hh])
@@ -783,9 +813,10 @@ class upFRG(nn.Module):
         self.h_blk = nn.Sequential(*[HFEBlock(dim, match_factor=1, ffn_expansion_factor=1)
                                      for _ in range(n_h_blocks)])
 
-    def forward(self, x_l, x_h, join=None):
+    def forward(self, x_l, x_h, join=None, synthesise=True):
         """`join`: makes a side-stream `x_h` (DownFRG.forward) an input of the current stream - called only after this
-        group's LFSS stack, which does not need it, has been issued."""
+        group's LFSS stack, which does not need it, has been issued.  `synthesise` False: the un-synthesised (low, high) pair
+        comes back, for a caller that folds the IWT into what reads it (UNet.forward)."""
         low = _run_lfss_stack(self.l_blk, x_l)
         qkv0 = None
         if join is not None:
@@ -793,7 +824,8 @@ class upFRG(nn.Module):
         for i, blk in enumerate(self.h_blk):
             x_h = blk(x_h, low, qkv=qkv0 if i == 0 else None)
         # reference: iwt(cat([x_l, h_out_conv(x_h)], 1)); the pair form skips the concatenation
-        return self.iwt(low, _conv(self.h_out_conv, x_h))
+        high = _conv(self.h_out_conv, x_h)
+        return self.iwt(low, high) if synthesise else (low, high)
 
 
 _SIDE_STREAMS = {}
@@ -868,7 +900,7 @@ class UNet(nn.Module):
                     d.append(_ps_conv(ps, img))
                     d_ready.append(side.record_event())
             img.record_stream(sides[0]); img.record_stream(sides[1]); img.record_stream(sides[2])
-        low, high1 = self.down_group1(_conv(self.conv_01, img), d[0], sides[0], d_ready[0])
+        low, high1 = self.down_group1(_conv_dwt(self.conv_01, img), d[0], sides[0], d_ready[0])
         low, high2 = self.down_group2(low, d[1], sides[1], d_ready[1])
         low, high3 = self.down_group3(low, d[2], sides[2], d_ready[2])
 
@@ -888,6 +920,9 @@ class UNet(nn.Module):
             return join
         low = self.up_group3(low, high3, joiner(sides[2], self.up_group3, high3))
         low = self.up_group2(low, high2, joiner(sides[1], self.up_group2, high2))
+        if _iwt_conv_fused(self, self.last, low, img):     # the level-1 synthesis inside `last`
+            low, high = self.up_group1(low, high1, joiner(sides[0], self.up_group1, high1), synthesise=False)
+            return ops.iwt_conv2d(low, high, self.last.weight, self.last.bias, img)
         low = self.up_group1(low, high1, joiner(sides[0], self.up_group1, high1))
         return _conv(self.last, low, residual=img)
 

@@ -58,7 +58,7 @@ static bool conv_ws_enabled(const wm::Conv2dArgs& a, int B, int th) {
     return ntiles >= 768;
 }
 
-template <int RW, int MT, bool G1X1 = false, bool EPI = false, int NPW = 4, bool F16 = false>
+template <int RW, int MT, bool G1X1 = false, bool EPI = false, int NPW = 4, bool F16 = false, bool DWTE = false, bool IWTI = false>
 static int conv2d_ws_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
     using Cfg = wm::ConvWsCfg<RW, MT, G1X1, NPW>;
     static bool configured[64] = {};
@@ -69,7 +69,7 @@ static int conv2d_ws_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
     {
         std::lock_guard<std::mutex> lk(mu);
         if (!configured[dev]) {
-            if (hipFuncSetAttribute((const void*)wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            if (hipFuncSetAttribute((const void*)wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16, DWTE, IWTI>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     Cfg::LDS_BYTES) != hipSuccess) return WM_EHIP;
             if (hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return WM_EHIP;
             configured[dev] = true;
@@ -79,7 +79,7 @@ static int conv2d_ws_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
     if (ntiles >= (1ll << 31)) return WM_EUNSUPPORTED;
     const int cus = std::max(8, ncu[dev] & ~7);
     const int G = (int)std::min<long long>(cus, ((ntiles + 7) / 8) * 8);
-    hipLaunchKernelGGL((wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16>), dim3((unsigned)G), dim3(256 + 64 * NPW), Cfg::LDS_BYTES, st, a, B);
+    hipLaunchKernelGGL((wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16, DWTE, IWTI>), dim3((unsigned)G), dim3(256 + 64 * NPW), Cfg::LDS_BYTES, st, a, B);
     return launch_status();
 }
 
@@ -306,6 +306,59 @@ int wm_conv2d_f16_steps(const float* x, const float* weight, const float* bias, 
     int rc = launch_status();
     if (rc) return rc;
     return conv2d_fwd_f16(x, wfrag, amax, bias, y, B, Cin, Cout, H, W, ks, stream);
+}
+
+// (ll, hl, lh, hh) = dwt(conv3x3(img) + bias): the wave-specialised kernel with the analysis epilogue (conv2d_ws.hip.h, DWTE) - the
+// first-generation kernel has no such form, so a call it would have to serve is refused.
+int wm_conv2d_dwt_fwd(const void* img, const void* wfrag, const float* bias, void* ll, void* hl, void* lh, void* hh, int B, int Cin,
+                      int Cout, int H, int W, int dtype, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (H % 2 || W % 2) return WM_EINVAL;
+    if (dtype != WM_F32 || Cout != 32) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!img || !wfrag || !ll || !hl || !lh || !hh) return WM_ENULL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = (const float*)img; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
+    a.bias = bias; a.gate = nullptr; a.res = nullptr; a.wfrag1 = nullptr; a.bias1 = nullptr;
+    a.y = (float*)ll; a.yband[0] = (float*)hl; a.yband[1] = (float*)lh; a.yband[2] = (float*)hh;
+    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = (Cin + 15) / 16; a.mtot = 1; a.mbase = 0; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    // the kernel's 32-bit byte offsets inside one batch element of the input and of the full-resolution output it stands for
+    if (conv_select_mode() == 1 || (long long)std::max(Cin, Cout) * H * W * 4 >= (1ll << 32)) return WM_EUNSUPPORTED;
+    ProfScope ps(13, st);
+    return conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1, false, true>(a, B, st);
+}
+
+// y = conv3x3(iwt(low, high)) + bias (+ residual): the wave-specialised kernel whose producers form the input tile from the bands
+// (conv2d_ws.hip.h, IWTI); refused where the first-generation kernel would have to serve the call.
+int wm_idwt_conv2d_fwd(const void* low, const void* high, const void* wfrag, const float* bias, const float* residual, float* y, int B,
+                       int Cin, int Cout, int H, int W, int dtype, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (H % 2 || W % 2) return WM_EINVAL;
+    if (dtype != WM_F32 || Cin != 32) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!low || !high || !wfrag || !y) return WM_ENULL;
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    Conv2dArgs a;
+    a.xa = (const float*)low; a.xb = (const float*)high; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
+    a.bias = bias; a.gate = nullptr; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
+    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 3 * Cin; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = Cin / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    // 32-bit byte offsets inside one batch element of `high` (3 Cin planes of H W / 4), of y and of the residual
+    if (conv_select_mode() == 1 || (long long)std::max(Cin, Cout) * H * W * 4 >= (1ll << 32)) return WM_EUNSUPPORTED;
+    ProfScope ps(13, st);
+    for (int mb = 0; mb < a.mtot; ++mb) {
+        a.mbase = mb;
+        const int rc = residual ? conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, true, 4, false, false, true>(a, B, st)
+                                : conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1, false, false, true>(a, B, st);
+        if (rc) return rc;
+    }
+    return WM_OK;
 }
 
 int wm_conv2d_gated_fwd(const float* xa, const float* xb, const int* xb_index, const void* wfrag3, const void* wfrag1,

@@ -56,6 +56,7 @@ struct Conv2dArgs {
     const uint4* wfrag1;              // G1X1 kernels: prepared 1x1 weights over the same input (PAConv.k2), else unused
     const float* bias1;               // G1X1: bias of that 1x1 (or null)
     float* y;                         // (B, Cout, H, W)
+    float* yband[3] = {nullptr, nullptr, nullptr};   // analysis epilogue (conv2d_ws.hip.h, DWTE): y = LL and these HL, LH, HH, each (B, Cout, H / 2, W / 2)
     int Ca, Cb, Cbsrc, Cout, H, W;
     int nch;                          // ceil((Ca + Cb) / 16) input-channel chunks
     int mtot;                         // ceil(Cout / 32) row tiles in wfrag

@@ -18,6 +18,7 @@
 #pragma once
 #include <type_traits>
 #include "conv2d.hip.h"
+#include "haar.hip.h"
 
 namespace wm {
 
@@ -82,10 +83,20 @@ __device__ __forceinline__ void ws_lds_store16(unsigned addr, const uint4& v) {
 
 __device__ __forceinline__ void ws_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int RW, int MT, bool G1X1, bool EPI, int NPW = 4, bool F16 = false>
+// the other pixel of a lane's 2x2 quad column pair: lane l <- lane l ^ 1 (one DPP move, quad_perm [1, 0, 3, 2])
+__device__ __forceinline__ float ws_from_pair_lane(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
+}
+
+// DWTE: the epilogue stores the Haar analysis of the output instead of the output (epilogue_dwt below): y = LL, yband = HL, LH, HH
+// IWTI: the input is the Haar synthesis of xa = LL (B, Ca, H / 2, W / 2) and xb = HL | LH | HH (B, 3 Ca, H / 2, W / 2), formed by the
+//       producers while they stage it (the *_iwt steps below)
+template <int RW, int MT, bool G1X1, bool EPI, int NPW = 4, bool F16 = false, bool DWTE = false, bool IWTI = false>
 __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kernel(const Conv2dArgs a, const int B) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cv_smem[];
     static_assert(!(F16 && G1X1), "the fp16 form (conv2d.hip.h) serves the plain convolutions of the training step");
+    static_assert(!DWTE || (MT == 1 && !G1X1 && !EPI && !F16 && RW % 2 == 0), "the analysis epilogue: one plain 32-channel row tile, whole quads per wave");
+    static_assert(!IWTI || (!G1X1 && !F16), "the synthesis staging: the plain bf16 form");
     const float sx = F16 ? cv_pow2_scale(a.amax[0]) : 1.0f;
     const float osc = F16 ? 1.0f / (sx * cv_pow2_scale(a.amax[1])) : 1.0f;
     using Cfg = ConvWsCfg<RW, MT, G1X1, NPW>;
@@ -112,7 +123,17 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
         const int ptid = tid - 256, pw = wave - 4;
         const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)cv_smem;
         static_assert(2 * NPIX * 16 < 65536, "the lo plane sits within the ds_write offset field");
-        float pin[2][2][PIT][8];                           // [set][k-half][pixel][channel]
+        // IWTI: a producer thread owns a 2x2 QUAD of the staged region, not PIT pixels of it: it loads the quad's four band values per
+        // channel (as many load instructions as pixels staged, not four times as many), runs haar_inv in iwt_init_pair's order and
+        // stages up to four pixels.  The staged region starts at the odd coordinates (h0 - 1, w0 - 1), so quads (h0 / 2 - 1 + qr,
+        // w0 / 2 - 1 + qc), qr < QR, qc < QC cover it; which of a quad's pixels lie inside it is the same for every tile.
+        constexpr int QR = (TH + 4) / 2, QC = (kWsTW + 4) / 2;
+        static_assert(!IWTI || QR * QC <= NPT, "one quad per producer thread");
+        constexpr int PSL = IWTI ? 4 : PIT;                // pin slots: the four bands of the quad | the thread's pixels
+        const int qr = IWTI ? ptid / QC : 0, qc = IWTI ? ptid - qr * QC : 0;      // (the other forms compute none of these)
+        const int h2 = IWTI ? a.H >> 1 : 0, w2 = IWTI ? a.W >> 1 : 0;
+        const unsigned HW2b = IWTI ? (unsigned)(h2 * w2) * 4u : 0u;
+        float pin[2][2][PSL][8];                           // [set][k-half][pixel | band][channel]
         // all-ones / zero per staged pixel of the set: inside the image?  Kept opaque to the compiler (an asm barrier
         // on the mask, not on the data): a select on a condition it can trace back to the load makes it predicate every
         // load per lane - one exec-masked branch and one wait per load
@@ -159,20 +180,28 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 ccf = 0; ++jf;
                 int b, h0, w0;
                 tl.locate(jf, TH, b, h0, w0);
+                if constexpr (IWTI) {                      // the quad's place in a band plane; a quad is inside the image whole or not at all
+                    const int qh = (h0 >> 1) - 1 + qr, qw = (w0 >> 1) - 1 + qc;
+                    const bool ok = qr < QR && qh >= 0 && qh < h2 && qw >= 0 && qw < w2;
+                    okF[0] = ok ? 0xffffffffu : 0u;
+                    poff[0] = ok ? (unsigned)(qh * w2 + qw) * 4u : 0u;
+                    asm volatile("" : "+v"(okF[0]), "+v"(poff[0]));
+                } else {
 #pragma unroll
-                for (int it = 0; it < PIT; ++it) {
-                    const int p = ptid + it * NPT;
-                    const int pr = p / PW, pc = p - pr * PW;
-                    const int h = h0 - 1 + pr, w = w0 - 1 + pc;
-                    const bool ok = p < NPIX && h >= 0 && h < H && w >= 0 && w < W;
-                    okF[it] = ok ? 0xffffffffu : 0u;
-                    poff[it] = ok ? (unsigned)(h * W + w) * 4u : 0u;
-                    asm volatile("" : "+v"(okF[it]), "+v"(poff[it]));
+                    for (int it = 0; it < PIT; ++it) {
+                        const int p = ptid + it * NPT;
+                        const int pr = p / PW, pc = p - pr * PW;
+                        const int h = h0 - 1 + pr, w = w0 - 1 + pc;
+                        const bool ok = p < NPIX && h >= 0 && h < H && w >= 0 && w < W;
+                        okF[it] = ok ? 0xffffffffu : 0u;
+                        poff[it] = ok ? (unsigned)(h * W + w) * 4u : 0u;
+                        asm volatile("" : "+v"(okF[it]), "+v"(poff[it]));
+                    }
                 }
                 if (b != bF) {                             // uniform; once per batch element
                     bF = b;
-                    xaF = a.xa + (long long)b * a.Ca * HW;
-                    xbF = a.xb ? a.xb + (long long)b * a.Cbsrc * HW : a.xa;
+                    xaF = a.xa + (long long)b * a.Ca * (IWTI ? (long long)h2 * w2 : HW);
+                    xbF = a.xb ? a.xb + (long long)b * a.Cbsrc * (IWTI ? (long long)h2 * w2 : HW) : a.xa;
                     if (a.xb_idx) {
                         const int* idx = a.xb_idx + (long long)b * a.Cb;
                         idxv0 = lane < a.Cb ? idx[lane] : 0;
@@ -190,43 +219,83 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
             if (half == 0) {
                 ccs[S] = ccf;
 #pragma unroll
-                for (int it = 0; it < PIT; ++it) okm[S][it] = okF[it];
+                for (int it = 0; it < (IWTI ? 1 : PIT); ++it) okm[S][it] = okF[it];
             }
             const int c0 = ccf * 16 + half * 8;            // first of the 8 channels (uniform)
-            const bool from_a = c0 < a.Ca;
-            const int cl = from_a ? c0 : c0 - a.Ca;
-            const int cn = (from_a ? a.Ca : a.Cb) - cl;
-            const char* src = reinterpret_cast<const char*>(from_a ? xaF : xbF);
-            const bool gather = !from_a && a.xb_idx;
+            if constexpr (IWTI) {                          // Ca % 8 == 0 (host check): no padded channel; band k of channel c is plane
+                const char* lowp = reinterpret_cast<const char*>(xaF);                   // (k - 1) Ca + c of xb
+                const char* highp = reinterpret_cast<const char*>(xbF);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const bool cok = j < cn;
-                const int cg = cl + j;
-                const int ch = !cok ? 0 : !gather ? cg
-                             : cg < 64 ? __builtin_amdgcn_readlane(idxv0, cg) : __builtin_amdgcn_readlane(idxv1, cg - 64);
-                const unsigned choff = (unsigned)ch * (unsigned)HW * 4u;
+                for (int j = 0; j < 8; ++j) {
+                    pin[S][half][0][j] = *reinterpret_cast<const float*>(lowp + (size_t)((unsigned)(c0 + j) * HW2b + poff[0]));
 #pragma unroll
-                for (int it = 0; it < PIT; ++it)
-                    pin[S][half][it][j] = *reinterpret_cast<const float*>(src + (size_t)(choff + poff[it]));
+                    for (int k = 0; k < 3; ++k)
+                        pin[S][half][1 + k][j] =
+                            *reinterpret_cast<const float*>(highp + (size_t)((unsigned)(k * a.Ca + c0 + j) * HW2b + poff[0]));
+                }
+            } else {
+                const bool from_a = c0 < a.Ca;
+                const int cl = from_a ? c0 : c0 - a.Ca;
+                const int cn = (from_a ? a.Ca : a.Cb) - cl;
+                const char* src = reinterpret_cast<const char*>(from_a ? xaF : xbF);
+                const bool gather = !from_a && a.xb_idx;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const bool cok = j < cn;
+                    const int cg = cl + j;
+                    const int ch = !cok ? 0 : !gather ? cg
+                                 : cg < 64 ? __builtin_amdgcn_readlane(idxv0, cg) : __builtin_amdgcn_readlane(idxv1, cg - 64);
+                    const unsigned choff = (unsigned)ch * (unsigned)HW * 4u;
+#pragma unroll
+                    for (int it = 0; it < PIT; ++it)
+                        pin[S][half][it][j] = *reinterpret_cast<const float*>(src + (size_t)(choff + poff[it]));
+                }
             }
         };
         auto stage_half = [&](auto SETC, auto HALFC, int buf) {
             constexpr int S = decltype(SETC)::value, half = decltype(HALFC)::value;
-            const unsigned s_in = lds_base + (unsigned)(buf * BUF + half * NPIX + ptid) * 16u;
-            const int c0 = ccs[S] * 16 + half * 8;
-            const int cn = c0 < a.Ca ? a.Ca - c0 : a.Ca + a.Cb - c0;       // valid channels of this 8-group (uniform)
+            if constexpr (IWTI) {
+                // staged pixel (2 qr - 1 + dr, 2 qc - 1 + dc) of the quad; haar_inv's a, b, c, d are (dr, dc) = (0, 0), (1, 0), (0, 1), (1, 1)
+                const unsigned s_q = lds_base + (unsigned)(buf * BUF + half * NPIX + (2 * qr - 1) * PW + 2 * qc - 1) * 16u;
+                float px4[4][8];
 #pragma unroll
-            for (int it = 0; it < PIT; ++it) {
-                const int p = ptid + it * NPT;
-                if (NPIX % NPT == 0 || p < NPIX) {
-                    Frag16 hi, lo;
+                for (int j = 0; j < 8; ++j) {
+                    float sb[4];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = j < cn ? __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pin[S][half][it][j]) & okm[S][it]) : 0.0f;
-                        cv_split<F16>(F16 ? v * sx : v, hi, lo, j);
+                    for (int k = 0; k < 4; ++k)
+                        sb[k] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pin[S][half][k][j]) & okm[S][0]);
+                    haar_inv<false>(sb[0], sb[1], sb[2], sb[3], px4[0][j], px4[1][j], px4[2][j], px4[3][j]);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int dr = q & 1, dc = q >> 1;
+                    const bool in = qr < QR && (dr ? qr < QR - 1 : qr > 0) && (dc ? qc < QC - 1 : qc > 0);
+                    if (in) {
+                        Frag16 hi, lo;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) cv_split<false>(px4[q][j], hi, lo, j);
+                        const unsigned ad = s_q + (unsigned)(dr * PW + dc) * 16u;
+                        ws_lds_store16<0>(ad, hi.u);
+                        ws_lds_store16<2 * NPIX * 16>(ad, lo.u);
                     }
-                    ws_lds_store16<0>(s_in + it * (NPT * 16u), hi.u);
-                    ws_lds_store16<2 * NPIX * 16>(s_in + it * (NPT * 16u), lo.u);
+                }
+            } else {
+                const unsigned s_in = lds_base + (unsigned)(buf * BUF + half * NPIX + ptid) * 16u;
+                const int c0 = ccs[S] * 16 + half * 8;
+                const int cn = c0 < a.Ca ? a.Ca - c0 : a.Ca + a.Cb - c0;       // valid channels of this 8-group (uniform)
+#pragma unroll
+                for (int it = 0; it < PIT; ++it) {
+                    const int p = ptid + it * NPT;
+                    if (NPIX % NPT == 0 || p < NPIX) {
+                        Frag16 hi, lo;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const float v = j < cn ? __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pin[S][half][it][j]) & okm[S][it]) : 0.0f;
+                            cv_split<F16>(F16 ? v * sx : v, hi, lo, j);
+                        }
+                        ws_lds_store16<0>(s_in + it * (NPT * 16u), hi.u);
+                        ws_lds_store16<2 * NPIX * 16>(s_in + it * (NPT * 16u), lo.u);
+                    }
                 }
             }
         };
@@ -436,6 +505,51 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
         }
     };
 
+    // The analysis form (DWTE; H, W even - host check): v = acc + bias as above, then haar_fwd on each 2x2 quad with
+    // haar_analysis_kernel's assignment a = (2i, 2j), b = (2i + 1, 2j), c = (2i, 2j + 1), d = (2i + 1, 2j + 1), stored at (i, j) of
+    // the four band tensors (B, Cout, H / 2, W / 2) - bit-identical to the convolution followed by wm_dwt2d_fwd, without the plane.
+    // Tile origins and RW are even: a quad is rows (r, r + 1) of one lane and the lane pair (px, px ^ 1), whose values one DPP
+    // move each brings over.  Even lanes store LL and HL, odd lanes LH and HH: 64 stores per wave and tile as in the plain form,
+    // all lanes active, 64-byte runs per band and half-wave; the band is a per-lane base pointer.  No load, so no vmcnt wait.
+    auto epilogue_dwt = [&](int j) {
+        int b, h0, w0;
+        const bool fast = tile_fast(j, b, h0, w0);
+        const int w = w0 + cw * 32 + px, hq = (h0 + rg * RW) >> 1;
+        const bool odd = px & 1;
+        const int h2 = H >> 1, w2 = W >> 1;
+        const unsigned HW2b = (unsigned)(h2 * w2) * 4u;
+        const size_t bo = (size_t)b * a.Cout * HW2b;
+        char* const y0 = reinterpret_cast<char*>(odd ? a.yband[1] : a.y) + bo;          // LL | LH
+        char* const y1 = reinterpret_cast<char*>(odd ? a.yband[2] : a.yband[0]) + bo;   // HL | HH
+        const int chb = a.mbase * 32 + 4 * khalf;
+        const unsigned o0 = (unsigned)((chb * h2 + hq) * w2 + (w >> 1)) * 4u;
+        float bv[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bv[i] = s_bias[4 * khalf + (i & 3) + 8 * (i >> 2)];
+        auto quads = [&](auto FASTC) {                    // FAST: interior tile, whole row tiles - the store path without predicates
+            constexpr bool FAST = decltype(FASTC)::value;
+#pragma unroll
+            for (int rp = 0; rp < RW / 2; ++rp) {
+                const bool in = FAST || (h0 + rg * RW + 2 * rp < H && w < W);  // (a quad is inside the image whole or not at all)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int dc = (i & 3) + 8 * (i >> 2);
+                    const float v0 = acc[0][2 * rp][i] + bv[i], v1 = acc[0][2 * rp + 1][i] + bv[i];
+                    const float n0 = ws_from_pair_lane(v0), n1 = ws_from_pair_lane(v1);     // (every lane takes part: before the predicate)
+                    float ll, hl, lh, hh;
+                    haar_fwd<false>(odd ? n0 : v0, odd ? n1 : v1, odd ? v0 : n0, odd ? v1 : n1, ll, hl, lh, hh);
+                    const unsigned o = o0 + (unsigned)(rp * w2) * 4u + (unsigned)dc * HW2b;
+                    if (FAST || (in && (full || chb + dc < a.Cout))) {
+                        *reinterpret_cast<float*>(y0 + (size_t)o) = odd ? lh : ll;
+                        *reinterpret_cast<float*>(y1 + (size_t)o) = odd ? hh : hl;
+                    }
+                }
+            }
+        };
+        if (fast) quads(std::true_type{});
+        else quads(std::false_type{});
+    };
+
     ws_barrier_lds();                                      // buffer 0 holds chunk 0
     int cc = 0, j = 0;
     for (int i = 0; i < n_it; ++i) {
@@ -445,8 +559,11 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
         ws_barrier_lds();                                  // this buffer is free; the other one is ready
         CV_STAMP(0, i, 2);
         if (++cc == nch) {
-            epilogue(j, M0{});
-            if (MT > 1) epilogue(j, M1{});
+            if constexpr (DWTE) epilogue_dwt(j);
+            else {
+                epilogue(j, M0{});
+                if (MT > 1) epilogue(j, M1{});
+            }
             zero_acc(M0{});
             if (MT > 1) zero_acc(M1{});
             cc = 0; ++j;

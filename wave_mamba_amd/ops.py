@@ -1321,6 +1321,104 @@ def dwconv_conv1x1(x, dw_weight, dw_bias, act, weight, bias=None, residual=None,
     return y
 
 
+# A 3x3 convolution whose only reader is the Haar analysis, as ONE kernel (wm_conv2d_dwt_fwd: the wave-specialised kernel forms the
+# four sub-bands of each 2x2 quad in its epilogue, the full-resolution plane between the two - 128 B per position written and read
+# back - never reaches HBM; bit-identical).  False (tests / tools): the two launches.
+_FUSE_CONV_DWT = True
+# UNet.conv_01 + down_group1's DWT take it per image (batch 1: the batch measured) from the smallest full-resolution map at which the
+# fused call measured faster than the pair - the smaller of the two measured; nothing below it is measured, so nothing smaller takes
+# it.  Per call, pair -> fused, median of 7 x 20 calls with [slowest fused, fastest pair] (tools/bench_fullres_ends.py,
+# profiles/fullres_ends/per_call.txt):
+#   2176 x 3840   0.663 -> 0.398 ms [0.399, 0.662]
+#   1088 x 1920   0.188 -> 0.099 ms [0.101, 0.187]
+_FUSE_CONV_DWT_MIN_POSITIONS = 1088 * 1920
+
+
+def _fuse_conv_dwt_map(B, H, W):
+    """Images whose conv_01 -> DWT pair runs as conv2d_dwt: batch 1 and at least as many positions as the smallest map at which it
+    measured faster than the pair (the entry's own limits are in conv2d_dwt_supported)."""
+    return _FUSE_CONV_DWT and B == 1 and H * W >= _FUSE_CONV_DWT_MIN_POSITIONS
+
+
+def conv2d_dwt_supported(x, weight):
+    """Operands wm_conv2d_dwt_fwd covers: fp32 on the GPU, a (32, Cin, 3, 3) weight, even H and W, a batch element of the input and
+    of the 32-channel plane inside the wave-specialised kernel's 32-bit offsets."""
+    return (x.is_cuda and x.dim() == 4 and weight.dim() == 4 and tuple(weight.shape) == (32, x.shape[1], 3, 3)
+            and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+            and x.shape[0] <= 65535 and max(32, x.shape[1]) * x.shape[2] * x.shape[3] * 4 < 2 ** 32)
+
+
+def conv2d_dwt(x, weight, bias=None):
+    """dwt_init(F.conv2d(x, weight, bias, padding=1)) -> (ll, hl, lh, hh), each (B, 32, H / 2, W / 2), in one kernel
+    (wm_conv2d_dwt_fwd): x (B, Cin, H, W) fp32, weight (32, Cin, 3, 3).  Bit-identical to dwt_init(conv2d(x, weight, bias)) - which
+    is what runs while the first-generation 3x3 kernel is pinned (wm_conv2d_select(1), through conv2d_select or by the host itself:
+    the entry then answers WM_EUNSUPPORTED, the form exists in the wave-specialised kernel only).  Forward only."""
+    _require_cuda("conv2d_dwt", x, weight, bias)
+    if not conv2d_dwt_supported(x, weight):
+        raise NotImplementedError("conv2d_dwt: fp32, a (32, Cin, 3, 3) weight, even H and W, the wave-specialised 3x3 kernel's limits")
+    B, Cin, H, W = x.shape
+    x = x.contiguous()
+    frag = _conv2d_wfrag(weight)
+    outs = [torch.empty((B, 32, H // 2, W // 2), dtype=torch.float32, device=x.device) for _ in range(4)]
+    rc = _launch(x.device, "wm_conv2d_dwt_fwd", x, frag, None if bias is None else bias.detach().contiguous(), *outs, B, Cin, 32, H, W,
+                 WM_F32, status=True)
+    if rc == _lib.WM_EUNSUPPORTED:                                 # (the operands are covered: the first-generation kernel is pinned)
+        return dwt_init(conv2d(x, weight, bias))
+    check(rc, "wm_conv2d_dwt_fwd")
+    return tuple(outs)
+
+
+# A Haar synthesis whose only reader is a 3x3 convolution, as ONE kernel (wm_idwt_conv2d_fwd: the producer waves of the
+# wave-specialised kernel form the input tile from the four bands of each 2x2 quad; the full-resolution plane - 128 B per position
+# written and read back - never reaches HBM; bit-identical).  False (tests / tools): the two launches.
+_FUSE_IWT_CONV = True
+# The last upFRG's IWT + UNet.last take it per image (batch 1: the batch measured) from the smallest full-resolution map at which the
+# fused call measured faster than the pair - the smaller of the two measured.  Per call, pair -> fused, median of 7 x 20 calls with
+# [slowest fused, fastest pair] (tools/bench_fullres_ends.py, profiles/fullres_ends/per_call.txt):
+#   2176 x 3840   0.971 -> 0.704 ms [0.706, 0.970]
+#   1088 x 1920   0.248 -> 0.179 ms [0.179, 0.248]
+_FUSE_IWT_CONV_MIN_POSITIONS = 1088 * 1920
+
+
+def _fuse_iwt_conv_map(B, H, W):
+    """Images (B, H, W: the full-resolution output) whose IWT -> last pair runs as iwt_conv2d: batch 1 and at least as many positions as
+    the smallest map at which it measured faster than the pair (the entry's own limits are in iwt_conv2d_supported)."""
+    return _FUSE_IWT_CONV and B == 1 and H * W >= _FUSE_IWT_CONV_MIN_POSITIONS
+
+
+def iwt_conv2d_supported(low, weight):
+    """Operands wm_idwt_conv2d_fwd covers: a (B, 32, h, w) fp32 low band on the GPU (its high bands: (B, 96, h, w)), a (Cout, 32, 3, 3)
+    weight, a batch element of the synthesised plane and of the output inside the wave-specialised kernel's 32-bit offsets."""
+    return (low.is_cuda and low.dim() == 4 and low.shape[1] == 32 and weight.dim() == 4 and tuple(weight.shape[1:]) == (32, 3, 3)
+            and low.dtype == torch.float32 and weight.dtype == torch.float32 and low.shape[0] <= 65535
+            and max(32, weight.shape[0]) * low.shape[2] * low.shape[3] * 16 < 2 ** 32)
+
+
+def iwt_conv2d(low, high, weight, bias=None, residual=None):
+    """F.conv2d(iwt_init_pair(low, high), weight, bias, padding=1) (+ residual) in one kernel (wm_idwt_conv2d_fwd): low (B, 32, h, w),
+    high (B, 96, h, w) fp32, weight (Cout, 32, 3, 3), residual (B, Cout, 2h, 2w) -> (B, Cout, 2h, 2w).  Bit-identical to
+    conv2d(iwt_init_pair(low, high), weight, bias, residual=residual) - which is what runs while the first-generation 3x3 kernel is
+    pinned (wm_conv2d_select(1): the entry then answers WM_EUNSUPPORTED).  Forward only."""
+    _require_cuda("iwt_conv2d", low, high, weight, bias, residual)
+    if not iwt_conv2d_supported(low, weight):
+        raise NotImplementedError("iwt_conv2d: fp32, 32-channel bands, a (Cout, 32, 3, 3) weight, the wave-specialised 3x3 kernel's limits")
+    B, C, h, w = low.shape
+    cout = weight.shape[0]
+    if tuple(high.shape) != (B, 3 * C, h, w) or high.dtype != torch.float32:
+        raise RuntimeError(f"iwt_conv2d: high must be float32 {(B, 3 * C, h, w)}, got {tuple(high.shape)}")
+    if residual is not None and (tuple(residual.shape) != (B, cout, 2 * h, 2 * w) or residual.dtype != torch.float32):
+        raise RuntimeError(f"iwt_conv2d: residual must be float32 {(B, cout, 2 * h, 2 * w)}, got {tuple(residual.shape)}")
+    frag = _conv2d_wfrag(weight)
+    y = torch.empty((B, cout, 2 * h, 2 * w), dtype=torch.float32, device=low.device)
+    rc = _launch(low.device, "wm_idwt_conv2d_fwd", low.contiguous(), high.contiguous(), frag,
+                 None if bias is None else bias.detach().contiguous(), None if residual is None else residual.contiguous(), y,
+                 B, C, cout, 2 * h, 2 * w, WM_F32, status=True)
+    if rc == _lib.WM_EUNSUPPORTED:                                 # (the operands are covered: the first-generation kernel is pinned)
+        return conv2d(iwt_init_pair(low, high), weight, bias, residual=residual)
+    check(rc, "wm_idwt_conv2d_fwd")
+    return y
+
+
 def patchify_conv_supported(img, weight, r):
     """Shapes wm_patchify_conv_fwd covers: nn.PixelUnshuffle(r) + 1x1 nn.Conv2d on an fp32 NCHW image."""
     return (img.is_cuda and img.dtype == torch.float32 and img.dim() == 4 and weight.dim() == 4 and r in (2, 4, 8)
