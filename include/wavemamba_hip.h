@@ -369,6 +369,26 @@ int wm_layernorm_tok_bwd(const float* x, const float* weight, const float* gy, f
 int wm_image_pre_u8(const uint8_t* image, float* out, int h, int w, int Hp, int Wp, int swap_rb, void* stream);
 int wm_image_post_u8(const float* in, uint8_t* image, int h, int w, int Hp, int Wp, int swap_rb, void* stream);
 
+/* A training batch from uint8 images on the device: the train phase of PairedImageDataset.__getitem__ after the decode
+ * (basicsr/data/paired_image_dataset.py:80-131 at scale 1) and the default collate, csrc/patch_batch.hip.h.  Per sample b the
+ * row table[b] = {lq_ptr, gt_ptr, h, w, top, left, mode, reserved} (int64 each; the two pointers are device addresses of
+ * contiguous (h, w, 3) uint8 images of one shape) yields lq[b] and gt[b], each (3, P, P) fp32:
+ *   padding   bottom / right to H = max(h, P), W = max(w, P) with cv2.BORDER_REFLECT (img_util.py:150-166): padded row y is source
+ *             row m < h ? m : 2 h - 1 - m, m = y mod 2 h, columns alike - the edge-including reflection (numpy 'symmetric'), not the
+ *             'reflect' of wm_image_pre_u8; no padded image is made;
+ *   crop      the window [top, top + P) x [left, left + P) of both (paired_random_crop, transforms.py:24-83);
+ *   augment   mode 0..7 of data_augmentation (transforms.py:223-268): identity, flipud, rot90, flipud(rot90), rot90 k=2,
+ *             flipud(rot90 k=2), rot90 k=3, flipud(rot90 k=3);
+ *   convert   channel-major, uint8 / 255 in fp32 (img2tensor, img_util.py:9-38); swap_rb: BGR -> RGB.
+ * Bit for bit what the reference's dataset and collate hand to feed_data.  One launch, every output element written (nothing is
+ * zeroed first), so it captures into a HIP graph; the table is read by the KERNEL, so rewriting it between replays changes the
+ * crops.  The host cannot check a device table: the kernel clamps top / left into [0, H - P] / [0, W - P] and uses mode & 7, and a
+ * row with h or w outside [1, 2^30] or a NULL image yields zeros - a wrong row selects a wrong window but never reads outside
+ * the image it names.  The pointers themselves are the caller's responsibility.  Images may start at any byte.
+ * WM_EINVAL: B < 0 or P <= 0; B == 0 is a no-op; WM_EALIGN: table not 8-byte, lq / gt not 4-byte aligned; WM_EUNSUPPORTED: more
+ * than 2^24 - 1 tiles of 32 x 32 (2 B ceil(P / 32)^2). */
+int wm_paired_patches_u8(const int64_t* table, float* lq, float* gt, int B, int P, int swap_rb, void* stream);
+
 /* dW (O, I) = gy^T x for token-major gy (T, O), x (T, I): weight gradient of nn.Linear (SS2D.in_proj / out_proj,
  * wavemamba_arch.py:345 / :386) in training.  (O, I) in {(128,32), (32,64), (64,16), (16,32), (32,16), (16,16), (64,32),
  * (32,32), (16,64)}: the in_proj / out_proj shapes of hidden_dim 32, 16, 8. */

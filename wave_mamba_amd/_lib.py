@@ -55,6 +55,7 @@ SIGNATURES = {
     "wm_layernorm_tok_bwd": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _i64, _i, _p]),
     "wm_image_pre_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "wm_image_post_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "wm_paired_patches_u8": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "wm_linear_wgrad": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
     "wm_conv2d_wgrad_workspace_bytes": (_sz, [_i] * 6),
     "wm_conv2d_wgrad": (_i, [_p, _p, _p, _p, _p, _sz] + [_i] * 6 + [_p]),

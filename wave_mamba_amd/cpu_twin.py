@@ -5,6 +5,8 @@ LOLv1 / 1x3x256x256 "CPU-only PyTorch forward (plumbing, no GPU)").
     iwt_init(_pair)     Haar synthesis              :113-130
     selective_scan_fn   the selective-scan operator :465-471 (mamba_ssm's published selective_scan_ref semantics)
     ss2d_core           SS2D.forward_core           :446-478 (for the torch.library op wavemamba_hip::ss2d_core on CPU tensors)
+    paired_patches      the train phase of PairedImageDataset.__getitem__ after the decode + default collate
+                        (/root/reference/basicsr/data/paired_image_dataset.py:80-131; host form of ops.paired_patches_u8)
 
 Plain PyTorch, differentiable by autograd, written from the operators' definitions.  They are
 the implementation for CPU TENSORS and nothing else: `ops.py` selects them by the device of the input, never by the absence of
@@ -140,3 +142,48 @@ def ssim_mean(img1, img2):
     c1, c2 = 0.01 ** 2, 0.03 ** 2
     s_map = ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2))
     return s_map.mean().to(img1.dtype)
+
+
+# out[i, j] = A[r, c] for the eight modes of data_augmentation (transforms.py:223-268): (r from j?, r mirrored?, c mirrored?)
+_AUG_MODES = ((False, False, False), (False, True, False), (True, False, True), (True, False, False),
+              (False, True, True), (False, False, True), (True, True, False), (True, True, True))
+
+
+def border_reflect_index(n_padded, n):
+    """Source indices of the first n_padded positions of an axis of n elements continued by cv2.BORDER_REFLECT
+    (...cba|abcdefgh|hgf..., the edge-including reflection, numpy's 'symmetric'): m = y mod 2n, m < n ? m : 2n - 1 - m."""
+    m = torch.arange(n_padded) % (2 * n)
+    return torch.where(m < n, m, 2 * n - 1 - m)
+
+
+def paired_patches(pairs, rows, gt_size, swap_rb=True):
+    """The reference's training batch from uint8 images (paired_image_dataset.py:80-131 at scale 1, then the default collate).
+    pairs: a sequence of (lq, gt) images, each (h, w, 3) uint8 (numpy arrays or CPU tensors; BGR as cv2 reads them, or RGB with
+    swap_rb=False); rows: (index into pairs, top, left, mode) per sample.  Per sample, for both images: pad bottom / right to at
+    least gt_size with cv2.BORDER_REFLECT (img_util.py:150-166), take the gt_size window at (top, left) (transforms.py:24-83),
+    apply mode 0..7 of data_augmentation (transforms.py:223-268; the index table of include/wavemamba_hip.h), reverse the channels
+    (swap_rb), HWC -> CHW, float32, / 255.  -> (lq, gt), each (B, 3, gt_size, gt_size) float32.  Rows out of range raise."""
+    P = int(gt_size)
+    ii, jj = torch.meshgrid(torch.arange(P), torch.arange(P), indexing="ij")
+    out = ([], [])
+    for index, top, left, mode in rows:
+        imgs = [torch.as_tensor(im) for im in pairs[index]]
+        if imgs[0].shape != imgs[1].shape:
+            raise ValueError(f"paired_patches: lq {tuple(imgs[0].shape)} and gt {tuple(imgs[1].shape)} differ in shape")
+        h, w = imgs[0].shape[:2]
+        H, W = max(h, P), max(w, P)
+        if not (0 <= top <= H - P and 0 <= left <= W - P and 0 <= mode <= 7):
+            raise ValueError(f"paired_patches: row {(index, top, left, mode)} outside a {h} x {w} image padded to {H} x {W}")
+        sy, sx = border_reflect_index(H, h)[top:top + P], border_reflect_index(W, w)[left:left + P]
+        turn, flip_r, flip_c = _AUG_MODES[mode]
+        r, c = (jj, ii) if turn else (ii, jj)
+        r, c = (P - 1 - r if flip_r else r), (P - 1 - c if flip_c else c)
+        for k, im in enumerate(imgs):
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                raise ValueError(f"paired_patches: expected (h, w, 3) uint8 images, got {tuple(im.shape)} {im.dtype}")
+            a = im[sy[r], sx[c]]                                  # (P, P, 3): out[i, j] = A[r, c], A = padded[top + ., left + .]
+            if swap_rb:
+                a = a.flip(-1)
+            out[k].append(a.permute(2, 0, 1).to(torch.float32) / 255.0)
+    empty = torch.empty(0, 3, P, P, dtype=torch.float32)
+    return tuple(torch.stack(o) if o else empty.clone() for o in out)

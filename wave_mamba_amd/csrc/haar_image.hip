@@ -1,10 +1,12 @@
-// haar_image.hip - C ABI over the Haar transforms, uint8 image I/O, the L1 and SSIM losses and the image-quality metrics.
+// haar_image.hip - C ABI over the Haar transforms, uint8 image I/O, training-batch formation, the L1 and SSIM losses and the
+// image-quality metrics.
 #include <initializer_list>
 #include "host_common.h"
 #include "haar.hip.h"
 #include "imageio.hip.h"
 #include "loss.hip.h"
 #include "metrics.hip.h"
+#include "patch_batch.hip.h"
 #include "ssim_loss.hip.h"
 
 namespace wm {
@@ -209,6 +211,20 @@ int wm_image_post_u8(const float* in, uint8_t* image, int h, int w, int Hp, int 
     if (h > 65535) return WM_EUNSUPPORTED;
     hipLaunchKernelGGL(image_post_kernel, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, (hipStream_t)stream,
                        in, image, h, w, Hp, Wp, swap_rb);
+    return launch_status();
+}
+
+// tiles of every sample's two images folded into grid.x; the same launch bound as the SSIM loss (SL_MAX_TILES workgroups of 256)
+int wm_paired_patches_u8(const int64_t* table, float* lq, float* gt, int B, int P, int swap_rb, void* stream) {
+    if (B < 0 || P <= 0) return WM_EINVAL;
+    if (B == 0) return WM_OK;
+    if (!table || !lq || !gt) return WM_ENULL;
+    if ((reinterpret_cast<uintptr_t>(table) & 7u) || ((reinterpret_cast<uintptr_t>(lq) | reinterpret_cast<uintptr_t>(gt)) & 3u)) return WM_EALIGN;
+    const long long tiles = ((long long)P + PB_TILE - 1) / PB_TILE;
+    if (tiles * tiles > SL_MAX_TILES || 2LL * B > SL_MAX_TILES / (tiles * tiles)) return WM_EUNSUPPORTED;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the table's fields are read as long long");
+    hipLaunchKernelGGL(paired_patches_kernel, dim3((unsigned)(tiles * tiles * 2 * B)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const long long*>(table), lq, gt, P, (int)tiles, swap_rb);
     return launch_status();
 }
 

@@ -1002,6 +1002,32 @@ def image_post_u8(t, h, w, swap_rb=True):
     return out
 
 
+def paired_patches_u8(table, P, swap_rb=True, out=None):
+    """A training batch from uint8 images resident on the device (wm_paired_patches_u8, include/wavemamba_hip.h): what the
+    reference's PairedImageDataset train phase and default collate produce at scale 1, bit for bit, in one launch.
+    table: (B, 8) int64 CUDA tensor, per sample (lq_ptr, gt_ptr, h, w, top, left, mode, reserved) - data.PairedPatchBatcher
+    writes it, and whoever writes it keeps the images alive.  The KERNEL reads it: a captured launch sees the table's contents
+    at replay time.  -> (lq, gt), each (B, 3, P, P) float32; `out=(lq, gt)` writes into the caller's tensors instead (contiguous
+    float32 of that shape on the table's device - GraphedTrainStep.lq / .gt, say)."""
+    _require_cuda("paired_patches_u8", table)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 8 or not table.is_contiguous():
+        raise RuntimeError(f"paired_patches_u8: expected a contiguous (B, 8) int64 table, got {tuple(table.shape)} {table.dtype}")
+    B, P = table.shape[0], int(P)
+    if out is None:
+        lq = torch.empty((B, 3, P, P), dtype=torch.float32, device=table.device)
+        gt = torch.empty_like(lq)
+    else:
+        lq, gt = out
+        for name, t in (("lq", lq), ("gt", gt)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != table.device
+                    or tuple(t.shape) != (B, 3, P, P) or not t.is_contiguous()):
+                raise RuntimeError(f"paired_patches_u8: out {name} must be a contiguous ({B}, 3, {P}, {P}) float32 tensor on "
+                                   f"{table.device}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}"
+                                   + (f" {t.dtype} on {t.device}, strides {t.stride()}" if isinstance(t, torch.Tensor) else ""))
+    _launch(table.device, "wm_paired_patches_u8", table, lq, gt, B, P, int(bool(swap_rb)))
+    return lq, gt
+
+
 def _metric_images(name, layout, *imgs):
     """uint8 CUDA images (H, W, 3) / (N, H, W, 3) for layout 'HWC', (3, H, W) / (N, 3, H, W) for 'CHW', all of one shape and
     device -> (4-D views, N, H, W, element strides (n, h, w, channel) shared by all of them)."""

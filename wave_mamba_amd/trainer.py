@@ -7,6 +7,16 @@ train_wavemamba_uhdll.yml:102-104; with `ssim_weight` the recipe's third term, s
 cal_ssim.py / femasr_model.py:29, :172 / yml:99-100, joins the sum), AdamW(lr 5e-4, weight_decay 1e-3, betas (0.9, 0.99)) (yml:75-79),
 DistributedDataParallel wrap with one gradient all-reduce per step (base_model.py:111-114; backend
 'nccl' == RCCL on ROCm), and the per-iteration loss reduce to rank 0 (base_model.py:376-401).
+
+Batches from images (data.py): the steps below take ready (B, 3, P, P) float32 `lq` / `gt`.  data.PairedPatchBatcher forms them on
+the device from resident uint8 images, as the reference's PairedImageDataset train phase and collate would (crop, one of eight
+flips / rotations, BGR -> RGB, CHW, / 255 - bit for bit), in one launch.  With a graphed step it writes straight into the graph's
+input buffers, so no copy_ sits between the batch and the replay:
+
+    step = GraphedTrainStep(net, optimizer, *batcher.form(first_indices))
+    run = graphed_step_with_batcher(step, batcher)
+    for indices in sampler:                            # B indices into the store per step
+        losses = run(indices)                          # batcher.form(indices, out=(step.lq, step.gt)); step()
 """
 import torch
 import torch.distributed as dist
@@ -281,6 +291,16 @@ class GraphedDDPTrainStep:
             self._exchange()
             self.graph_b.replay()
         return self.losses
+
+
+def graphed_step_with_batcher(step, batcher):
+    """The training loop's body for a GraphedTrainStep / GraphedDDPTrainStep fed by a data.PairedPatchBatcher: returns
+    run(indices=None, rows=None), which forms the batch directly in the step's input buffers (one launch on the current stream,
+    no copy_) and replays the step on them.  Returns the step's loss dict."""
+    def run(indices=None, rows=None):
+        batcher.form(indices, rows, out=(step.lq, step.gt))
+        return step()
+    return run
 
 
 def loss_values(loss_dict):
