@@ -298,6 +298,17 @@ int wm_conv2d_ln_fwd(const float* x, const float* ln_weight, const float* ln_bia
 int wm_dwconv_conv1x1_fwd(const float* x, int64_t x_batch_stride, const float* dw_weight, const float* dw_bias, int act,
                           const void* wfrag, const float* bias, const float* residual, float* y, int B, int C, int Cout, int H,
                           int W, void* stream);
+/* The two heads of an HFE block as ONE kernel each: norm1 -> attn.qkv -> qkv_dwconv on the q | k channels (wavemamba_arch.py:768-771,
+ * Cout = 96, Cdw = 64) and norm2 -> ffn.project_in (:733-736, Cout = Cdw = 32).
+ *   y[:, :Cdw] = dwconv3x3(conv1x1(LayerNorm2d(x)) + bias)[:, :Cdw] + dw_bias      y[:, Cdw:] = (conv1x1(LayerNorm2d(x)) + bias)[:, Cdw:]
+ * Bit-identical to wm_conv2d_ln_fwd followed by wm_dwconv3x3_fwd on the first Cdw channels; the plane between them (2 x 4 Cdw bytes
+ * per position) never exists.  x (B, 32, H, W); `wfrag` from wm_conv2d_prep(weight (Cout, 32, 1, 1)); dw_weight (Cdw, 1, 3, 3); bias
+ * (Cout) and dw_bias (Cdw) may be NULL; y (B, Cout, H, W) aliases no input.  band_rows: output rows per band of the row walk, 0 = the
+ * entry's choice (tests force several bands on small maps).  Cin == 32, (Cout, Cdw) in {(96, 64), (32, 32)} and H W < 2^25 only
+ * (WM_EUNSUPPORTED otherwise: use the two calls). */
+int wm_ln_conv1x1_dwconv_fwd(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* wfrag,
+                             const float* bias, const float* dw_weight, const float* dw_bias, float* y, int B, int Cin, int Cout,
+                             int Cdw, int H, int W, int band_rows, void* stream);
 /* The training form of the same convolutions (the F.conv2d calls of wavemamba_arch.py under autograd, femasr_model.py:170-181:
  * forward, and - on the transposed, flipped weight - the input gradient): fp16 matrix cores, two-term split of both operands
  * (22 significant bits, fp32-class: ~1e-7 relative to an fp64 convolution instead of the bf16 form's 3-4e-6, which the

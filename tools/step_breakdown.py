@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""Per-step kernel-time breakdown from a rocprofv3 --kernel-trace CSV of bench.py (steps delimited by the three
-Haar analysis launches of a forward).  python tools/step_breakdown.py <bench_kernel_trace.csv> [nsteps]"""
-import collections, csv, sys
+"""Per-step kernel-time breakdown from a rocprofv3 --kernel-trace CSV of bench.py (steps delimited by the first
+kernel that runs once per forward).  python tools/step_breakdown.py <bench_kernel_trace.csv> [nsteps]"""
+import collections, csv, functools, math, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 idx = [i for i, r in enumerate(rows) if 'selscan_chunk_kernel' in r['Kernel_Name']]
 rows = rows[:idx[0]] if idx else rows              # drop the op-boundary scan leg that follows the timed region
-ha = [i for i, r in enumerate(rows) if 'haar_analysis' in r['Kernel_Name']]
-starts = ha[0::3]
+# a forward starts at the first kernel that runs once per forward.  Forwards in the trace: the greatest common divisor of the
+# dispatch counts that at least two kernel names share (a kernel of the forward runs a multiple of it; copies and one-off preparation
+# kernels have counts of their own).  (Until the level-1 analysis moved into conv_01's kernel the three Haar analysis launches
+# delimited the steps.)
+cnt = collections.Counter(r['Kernel_Name'] for r in rows)
+once = functools.reduce(math.gcd, [c for c, k in collections.Counter(cnt.values()).items() if k >= 2 and c >= 5])
+first = next(r['Kernel_Name'] for r in rows if cnt[r['Kernel_Name']] == once)
+starts = [i for i, r in enumerate(rows) if r['Kernel_Name'] == first]
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 # `bench.py --full --steps 5 --warmup 3 --timed-only`: 3 warm-up + 5 timed forwards; use timed steps 2..4 (the last one has no
 # successor to delimit it)

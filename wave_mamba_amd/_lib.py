@@ -81,6 +81,7 @@ SIGNATURES = {
     "wm_conv2d_fwd": (_i, [_p] * 8 + [_i] * 8 + [_p]),
     "wm_conv2d_ln_fwd": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _p] + [_i] * 5 + [_p]),
     "wm_dwconv_conv1x1_fwd": (_i, [_p, _i64, _p, _p, _i, _p, _p, _p, _p] + [_i] * 5 + [_p]),
+    "wm_ln_conv1x1_dwconv_fwd": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _p, _p] + [_i] * 7 + [_p]),
     "wm_patchify_conv_fwd": (_i, [_p] * 4 + [_i] * 6 + [_p]),
     "wm_conv2d_f16_steps": (_i, [_p] * 6 + [_i] * 7 + [_p]),
     "wm_conv2d_gated_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p]),

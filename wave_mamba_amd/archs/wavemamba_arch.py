@@ -155,6 +155,20 @@ def _dw_pw_fused(x, dw_weight, pw_weight):
                 and _hip_ops._fuse_dw_pw_map(x.shape[0], x.shape[2], x.shape[3]))
 
 
+def _pw_dw_fused(norm, conv, dw_weight, x):
+    """norm -> the 1x1 `conv` -> a depth-wise 3x3 (weight `dw_weight`) that alone reads the 1x1's first len(dw_weight) channels runs as
+    ONE kernel (ops.ln_conv1x1_dwconv: the plane between the 1x1 and the depth-wise conv never reaches HBM, bit-identical to the two
+    launches): the site would take conv2d_ln, the backend has the fused call and covers the operands - one of the two HFE heads -,
+    nothing wants gradients (forward only), and the map is one the HIP library's size rule sends there (ops._fuse_pw_dw_map: one
+    measured floor per head; smaller maps keep the pair).  The caller adds `_needs_grad` of the depth-wise module."""
+    ops = _OpsBackend.impl
+    if norm is None or not (_op("conv2d_ln") and _op("ln_conv1x1_dwconv") and ops.conv2d_ln_supported(x, conv.weight)):
+        return False
+    head = ops.ln_conv1x1_dwconv_supported(x, conv.weight, dw_weight, dw_weight.shape[0])
+    return bool(head and _hip_ops._fuse_pw_dw_map(x.shape[0], x.shape[2], x.shape[3], head)
+                and not _needs_grad(conv, x) and not _needs_grad(norm))
+
+
 def _conv_dwt_fused(conv, img):
     """The 3x3 convolution `conv` of `img` and the Haar analysis that alone reads its output run as ONE kernel (ops.conv2d_dwt):
     the backend has it and covers the operands, nothing wants gradients (forward only), and the image is one the HIP library's size
@@ -572,7 +586,13 @@ class FeedForward(nn.Module):
 
     def forward(self, x, perception, residual=None, norm=None):
         """`norm`: the block's norm2, applied to `x` here (so that it can ride in project_in's 1x1 kernel)"""
-        y = _dwconv(self.project_in[1], _ln_conv(norm, self.project_in[0], x))
+        pw_in, dw_in = self.project_in
+        if _pw_dw_fused(norm, pw_in, dw_in.weight, x) and not _needs_grad(dw_in):
+            # project_in = [1x1, depth-wise 3x3] behind the block's norm2 in one kernel
+            y = _OpsBackend.impl.ln_conv1x1_dwconv(x, norm.weight, norm.bias, norm.eps, pw_in.weight, pw_in.bias, dw_in.weight,
+                                                   dw_in.bias, dw_in.weight.shape[0])
+        else:
+            y = _dwconv(dw_in, _ln_conv(norm, pw_in, x))
         if perception is not None:
             y = self.matching_transformation(y, perception)
         dw, pw = self.project_out[0], self.project_out[2]
@@ -604,20 +624,27 @@ class CMTAttention(nn.Module):
         """The part of `forward` that needs `x` alone (UNet.forward runs it ahead of time on a side stream).  `norm`: the
         block's norm1, applied to `x` here (it rides in the qkv 1x1 kernel).  Returns dwconv(qkv(norm(x))) - or, where the value
         third's depth-wise conv can ride in the folded project_out (inference, batch 1: the q | k channels of one image are
-        contiguous), the pair (dwconv of the q | k channels, qkv(norm(x)) itself): `forward` takes both forms."""
-        pre = _ln_conv(norm, self.qkv, x)
+        contiguous), the pair (dwconv of the q | k channels, the value third of qkv(norm(x)) itself): `forward` takes both forms.
+        That pair comes from ONE kernel where the size rule allows (_pw_dw_fused)."""
         dw = self.qkv_dwconv
-        c = pre.shape[1] // 3
+        c = self.qkv.weight.shape[0] // 3
         ops = _OpsBackend.impl
+        dw_qk = (dw.weight[:2 * c], None if dw.bias is None else dw.bias[:2 * c])     # the q | k part of the depth-wise conv
+        # (the value plane will have x's shape, dtype and device: the fold's operand test can run before it exists)
+        if (x.shape[0] == 1 and _op("attn_fold") and _op("dwconv3x3") and _pw_dw_fused(norm, self.qkv, dw_qk[0], x)
+                and _dw_pw_fused(x, dw.weight[2 * c:], self.project_out.weight) and not _needs_grad(self, x)):
+            y = ops.ln_conv1x1_dwconv(x, norm.weight, norm.bias, norm.eps, self.qkv.weight, self.qkv.bias, *dw_qk, 2 * c)
+            return y[:, :2 * c], y[:, 2 * c:]
+        pre = _ln_conv(norm, self.qkv, x)
         if (pre.shape[0] == 1 and _op("attn_fold") and _op("dwconv3x3") and ops.dwconv3x3_supported(pre)
                 and _dw_pw_fused(pre[:, 2 * c:], dw.weight[2 * c:], self.project_out.weight) and not _needs_grad(self, pre)):
-            return ops.dwconv3x3(pre[:, :2 * c], dw.weight[:2 * c], None if dw.bias is None else dw.bias[:2 * c]), pre
+            return ops.dwconv3x3(pre[:, :2 * c], *dw_qk), pre[:, 2 * c:]
         return _dwconv(dw, pre)
 
     def forward(self, x, perception, residual=None, qkv=None, norm=None):
         qkv = self.qkv_of(x, norm) if qkv is None else qkv
         pre = None
-        if isinstance(qkv, tuple):                         # (dwconv of q | k, the qkv 1x1's output): v's depth-wise conv is still to come
+        if isinstance(qkv, tuple):                         # (dwconv of q | k, the value third of the qkv 1x1's output): v's depth-wise conv is still to come
             qk, pre = qkv
             (q, k), v = qk.chunk(2, dim=1), None
         else:
@@ -628,7 +655,7 @@ class CMTAttention(nn.Module):
         dw_v = (dw.weight[2 * c:], None if dw.bias is None else dw.bias[2 * c:])      # the value third of the depth-wise conv
 
         def value():                                       # v; where the fold was not taken after all, a plain depth-wise conv of the slice
-            return v if pre is None else _OpsBackend.impl.dwconv3x3(pre[:, 2 * c:], *dw_v)
+            return v if pre is None else _OpsBackend.impl.dwconv3x3(pre, *dw_v)
         if self.matching is True:
             q = self.matching_transformation(q, perception)
         heads = self.num_heads
@@ -646,8 +673,8 @@ class CMTAttention(nn.Module):
                 # project_out(softmax(...) @ v) = (W_po @ blockdiag(attn)) @ v: a tiny kernel folds the (c/heads)^2
                 # attention into the 1x1 weight, the 1x1 convolution kernel applies it (+ bias, + residual)
                 wf = ops.attn_fold(G, nq, nk, self.temperature.reshape(heads), self.project_out.weight, b, heads)
-                if pre is not None:                        # batch 1: v = dwconv(pre[:, 2c:]) inside the folded 1x1's kernel
-                    return ops.dwconv_conv1x1(pre[:, 2 * c:], *dw_v, "none", wf[0].view(c, c, 1, 1), self.project_out.bias,
+                if pre is not None:                        # batch 1: v = dwconv(value third of the qkv 1x1) inside the folded 1x1's kernel
+                    return ops.dwconv_conv1x1(pre, *dw_v, "none", wf[0].view(c, c, 1, 1), self.project_out.bias,
                                               residual=residual, dynamic_weight=True)
                 outs = [ops.conv2d(v[i:i + 1], wf[i].view(c, c, 1, 1), self.project_out.bias,
                                    residual=None if residual is None else residual[i:i + 1], dynamic_weight=True)

@@ -1,10 +1,11 @@
 // conv.hip - C ABI over the dense convolutions (first-generation and wave-specialised kernels), the patchify convolution and the
-// depth-wise 3x3 folded into a 1x1 (dw_pw.hip.h).
+// depth-wise 3x3 folded into a 1x1 (dw_pw.hip.h) and its mirror image behind a LayerNorm (pw_dw.hip.h).
 #include "host_common.h"
 #include "conv2d.hip.h"
 #include "conv2d_ws.hip.h"
 #include "patchify.hip.h"
 #include "dw_pw.hip.h"
+#include "pw_dw.hip.h"
 
 using namespace wm;
 
@@ -241,6 +242,39 @@ int wm_dwconv_conv1x1_fwd(const float* x, int64_t x_batch_stride, const float* d
         if (residual) hipLaunchKernelGGL((dw_pw_kernel<false, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((dw_pw_kernel<false, false>), grid, dim3(256), 0, st, a);
     }
+    return launch_status();
+}
+
+// y[:, :Cdw] = dwconv3x3(conv1x1(LayerNorm2d(x)) + bias)[:, :Cdw] + dw_bias, y[:, Cdw:] = (conv1x1(LayerNorm2d(x)) + bias)[:, Cdw:] in one
+// kernel (pw_dw.hip.h): bit-identical to wm_conv2d_ln_fwd + wm_dwconv3x3_fwd on the first Cdw channels, without the plane between them.
+int wm_ln_conv1x1_dwconv_fwd(const float* x, const float* ln_weight, const float* ln_bias, float ln_eps, const void* wfrag,
+                             const float* bias, const float* dw_weight, const float* dw_bias, float* y, int B, int Cin, int Cout,
+                             int Cdw, int H, int W, int band_rows, void* stream) {
+    if (B < 0 || Cin <= 0 || Cout <= 0 || Cdw <= 0 || H < 0 || W < 0 || band_rows < 0) return WM_EINVAL;
+    const bool qkv = Cout == 96 && Cdw == 64, pin = Cout == 32 && Cdw == 32;
+    if (Cin != 32 || !(qkv || pin)) return WM_EUNSUPPORTED;          // the two HFE heads; callers run the two calls otherwise
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!x || !ln_weight || !ln_bias || !wfrag || !dw_weight || !y) return WM_ENULL;
+    if ((long long)H * W >= (1ll << 25)) return WM_EUNSUPPORTED;     // a 32-plane output tile is one raw buffer of < 2^32 bytes
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    PwDwArgs a;
+    a.x = x; a.ln_w = ln_weight; a.ln_b = ln_bias; a.ln_eps = ln_eps; a.wfrag = (const uint4*)wfrag; a.bias = bias;
+    a.dw_w = dw_weight; a.dw_b = dw_bias; a.y = y; a.H = H; a.W = W;
+    a.nstrips = (W + kPwDwCols - 1) / kPwDwCols;
+    // rows per band (a band recomputes two x rows of its neighbours): 8 where that still deals every SIMD of a 256-unit chip two
+    // walks, else 4 - UHD levels 1 and 2: 8704 / 2176 walks of 8 rows, level 3: 1088 of 4.  Taller bands measured slower at every
+    // level, by up to a third: at 2176 walks of 32 rows level 1 is 544 workgroups for the 512 the chip holds at two waves per SIMD -
+    // a second, nearly empty round (tools/bench_hfe_heads.py --band-rows, profiles/hfe_heads/per_call_band_rows.txt)
+    a.rows = band_rows ? band_rows : ((long long)B * a.nstrips * ((H + 7) / 8) >= 2048 ? 8 : 4);
+    a.nbands = (H + a.rows - 1) / a.rows;
+    a.nwalks = (long long)B * a.nbands * a.nstrips;
+    const long long nblocks = ((a.nwalks + 3) / 4 + 7) / 8 * 8;       // a multiple of 8: the kernel deals contiguous runs to the XCDs
+    if (nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
+    const dim3 grid((unsigned)nblocks);
+    ProfScope ps(14, st);
+    if (qkv) hipLaunchKernelGGL((pw_dw_kernel<3, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw_dw_kernel<1, 1>), grid, dim3(256), 0, st, a);
     return launch_status();
 }
 

@@ -26,6 +26,13 @@ __device__ __forceinline__ float dpp_from_upper_lane(float own_if_last, float v)
                                                                  0x130 /* wave_shl:1 */, 0xf, 0xf, false));
 }
 
+// `bytes` of memory from `p` as a raw buffer (the one place the descriptor's flags word is written): a load or store whose offset is
+// >= bytes reads zero / is dropped
+template <typename TP>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const TP* p, int bytes) {                                 // wave-uniform
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<TP*>(p), 0, bytes, 0x00020000);
+}
+
 constexpr int kDwRows = 16;     // output rows per thread strip (the kernels' `rows` argument: 16, or 8 / 4 where 16 leave the chip short of waves)
 
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }

@@ -29,14 +29,14 @@
 //                                      projection runs through it, so lfss_out's K order (acc_chan) is the same in
 //                                      lfss_out_mfma, lfss_out_conv_mfma and lfss_out_conv_acc by construction
 //   store_rows64                       two tiles of a row block -> 256-byte runs of a plane
-//   raw_rsrc, plane_rsrc, buf_ld, load_dw_taps   memory / one channel plane as a raw buffer; a channel's taps from LDS
+//   plane_rsrc, buf_ld, load_dw_taps             memory / one channel plane as a raw buffer (raw_rsrc: dwconv.hip.h); a channel's taps from LDS
 //   dw_taps9, dw_taps3 (dwconv.hip.h)  the depth-wise sum in the depth-wise kernel's own order; one kernel row of it (lfss_in_conv
 //                                      continues three output rows' chains with each x row)
 //   lfss_in_conv_band_rows             rows per band of lfss_in_conv (host)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "haar.hip.h"          // bf16_t, ld1 / st1 (fp32 and bf16 overloads)
-#include "dwconv.hip.h"        // dw_taps9, gelu_erf, dpp_from_lower_lane / dpp_from_upper_lane
+#include "dwconv.hip.h"        // dw_taps9, gelu_erf, dpp_from_lower_lane / dpp_from_upper_lane, raw_rsrc
 
 // ---- tuning switches (tools/build_variant.sh and tools/bench_lfss_rz.py pass them with -D) --------------------------
 // waves per SIMD the middle kernel is compiled for.  Four (128 registers) spilled 46 vector registers of the ny = 4 fp32
@@ -73,13 +73,6 @@ __device__ __forceinline__ float silu_fast(float v) {
 }
 __device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32); }
 __device__ __forceinline__ lfss_v16f mfma32(float a, float b, lfss_v16f acc) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0); }
-
-// `bytes` of memory from `p` as a raw buffer (the one place the descriptor's flags word is written): a load or store whose offset is
-// >= bytes reads zero / is dropped
-template <typename TP>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const TP* p, int bytes) {                                 // wave-uniform
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<TP*>(p), 0, bytes, 0x00020000);
-}
 
 // waves each take `gpw` consecutive groups of 64 positions; chosen so that the waves fill whole rounds of the
 // `slots` resident waves (1024 SIMDs x the kernel's waves per SIMD), at most 8 groups per wave

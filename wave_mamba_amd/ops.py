@@ -1347,6 +1347,58 @@ def dwconv_conv1x1(x, dw_weight, dw_bias, act, weight, bias=None, residual=None,
     return y
 
 
+# LayerNorm2d -> 1x1 -> the depth-wise 3x3 that alone reads the 1x1's first channels, as ONE kernel (wm_ln_conv1x1_dwconv_fwd: the plane
+# between the 1x1 and the depth-wise conv never reaches HBM; bit-identical): the two heads of an HFE block - "qkv" (32 -> 96, the
+# depth-wise conv on the 64 q | k channels, 512 of the pair's 1024 B per position) and "project_in" (32 -> 32, 256 of 512 B).
+# False (tests / tools): wm_conv2d_ln_fwd + wm_dwconv3x3_fwd.
+_FUSE_PW_DW = True
+# One floor per head: the positions PER IMAGE of the smallest UHD level at which that head's fused call measured faster than the pair
+# (its slowest repetition below the pair's fastest) - never below level 3, the smallest level there is: nothing below it is measured,
+# so nothing smaller takes the fused call.  Per call, pair -> fused, median of 7 x 20 alternating calls with [slowest fused, fastest
+# pair] (tools/bench_hfe_heads.py, profiles/hfe_heads/per_call.txt):
+#   UHD level 1 (1088 x 1920)  qkv 0.518 -> 0.295 ms [0.300, 0.517]   project_in 0.242 -> 0.169 ms [0.176, 0.240]
+#   UHD level 2 ( 544 x  960)  qkv 0.135 -> 0.090 ms [0.091, 0.134]   project_in 0.059 -> 0.043 ms [0.044, 0.059]
+#   UHD level 3 ( 272 x  480)  qkv 0.034 -> 0.034 ms [0.036, 0.034]: no gain - the qkv head keeps the pair there
+#                              project_in 0.025 -> 0.020 ms [0.021, 0.025]
+_FUSE_PW_DW_MIN_POSITIONS = {"qkv": 544 * 960, "project_in": 272 * 480}
+_PW_DW_HEADS = {"qkv": (96, 64), "project_in": (32, 32)}               # head -> (Cout, Cdw)
+
+
+def _fuse_pw_dw_map(B, H, W, head):
+    """Maps on which the HFE head `head` takes ln_conv1x1_dwconv: inside the entry's offset range (H W < 2^25) and, per image, at least
+    as large as the smallest map at which it measured faster than the pair."""
+    floor = _FUSE_PW_DW_MIN_POSITIONS[head]
+    return bool(_FUSE_PW_DW and B > 0 and floor <= H * W < (1 << 25))
+
+
+def ln_conv1x1_dwconv_supported(x, weight, dw_weight, n_dw):
+    """Operands wm_ln_conv1x1_dwconv_fwd covers: fp32 on the GPU, 32 input channels, (Cout, channels under the depth-wise conv) one of
+    the two HFE heads'.  Returns the head's name, or None."""
+    if not (x.is_cuda and x.dim() == 4 and x.shape[1] == 32 and weight.dim() == 4 and tuple(weight.shape[1:]) == (32, 1, 1)
+            and tuple(dw_weight.shape) == (n_dw, 1, 3, 3) and all(t.dtype == torch.float32 for t in (x, weight, dw_weight))):
+        return None
+    return next((h for h, form in _PW_DW_HEADS.items() if form == (weight.shape[0], n_dw)), None)
+
+
+def ln_conv1x1_dwconv(x, ln_w, ln_b, eps, weight, bias, dw_weight, dw_bias, n_dw, band_rows=0):
+    """y[:, :n_dw] = F.conv2d(pre, dw_weight, dw_bias, padding=1, groups=n_dw) of the first n_dw channels of pre = F.conv2d(LayerNorm2d(x),
+    weight, bias), y[:, n_dw:] = pre[:, n_dw:], in one kernel (wm_ln_conv1x1_dwconv_fwd): x (B, 32, H, W) fp32, weight (Cout, 32, 1, 1),
+    dw_weight (n_dw, 1, 3, 3), (Cout, n_dw) = (96, 64) or (32, 32).  Bit-identical to conv2d_ln() + dwconv3x3().  Forward only.
+    band_rows: output rows per band of the kernel's row walk (0: the entry's choice)."""
+    _require_cuda("ln_conv1x1_dwconv", x, ln_w, ln_b, weight, bias, dw_weight, dw_bias)
+    if ln_conv1x1_dwconv_supported(x, weight, dw_weight, n_dw) is None:
+        raise NotImplementedError("ln_conv1x1_dwconv: fp32, 32 input channels, (Cout, n_dw) = (96, 64) or (32, 32)")
+    B, C, H, W = x.shape
+    cout = weight.shape[0]
+    x = x.contiguous()
+    frag = _conv2d_wfrag(weight)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    _launch(x.device, "wm_ln_conv1x1_dwconv_fwd", x, _w(ln_w), _w(ln_b), float(eps), frag,
+            None if bias is None else bias.detach().contiguous(), _w(dw_weight), None if dw_bias is None else _w(dw_bias), y,
+            B, C, cout, n_dw, H, W, int(band_rows))
+    return y
+
+
 # A 3x3 convolution whose only reader is the Haar analysis, as ONE kernel (wm_conv2d_dwt_fwd: the wave-specialised kernel forms the
 # four sub-bands of each 2x2 quad in its epilogue, the full-resolution plane between the two - 128 B per position written and read
 # back - never reaches HBM; bit-identical).  False (tests / tools): the two launches.
