@@ -42,7 +42,8 @@ extern "C" {
 #define WM_F32 0
 #define WM_BF16 1
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change; entry points that are only ADDED - the _det forms and the channel
+ * gather - change no signature a caller compiled against 34 uses, so they do not bump it). */
 int wm_abi_version(void);
 /* Identity of the sources this binary was compiled from: the first 16 hex digits of a sha256 over csrc/ and this header
  * (wave_mamba_amd/build.py passes it as -DWM_BUILD_ID; "unknown" for a bare hipcc build).  Measurements that describe
@@ -523,7 +524,8 @@ int wm_patchify_conv_fwd(const float* img, const float* weight, const float* bia
  *               (+ the merged-output sum), 9 wm_lfss_mid_fwd, 10 ss2d core chunk-reduce (+ the parameter prep),
  *               11 wm_lfss_out_fwd / wm_lfss_out_conv_fwd, 12 selective-scan backward (all phases),
  *               13 dense 3x3 convolution, 14 1x1 convolution, 15 SKFF (all three kernels), 16 LayerNorm2d,
- *               17 depth-wise conv without SiLU (HFE branch, ffn), 18 wm_patchify_conv_fwd, 19 unused
+ *               17 depth-wise conv without SiLU (HFE branch, ffn), 18 wm_patchify_conv_fwd,
+ *               19 the fixed-order finish of the wm_*_det entry points (one launch per deterministic call)
  * wm_prof_enable(mask): bit k of `mask` switches recording for kernel id k (0 = off, ~0u = every class);
  * a non-zero mask also clears what was recorded before.  Two hipEventRecord calls cost ~10 us of stream
  * time per launch, so a caller timing a whole step enables only the classes it needs.
@@ -549,6 +551,71 @@ int wm_prof_collect(int* launches /*[WM_PROF_NKERNELS]*/, double* total_ms /*[WM
  * Process-wide, thread-safe.  No reference counterpart (the reference's gradients come from ATen). */
 int wm_zero_arena_register(void* base, size_t bytes);
 int wm_zero_arena_unregister(void* base);
+
+/* --------------------------------------------------------------------------------------------
+ * Deterministic forms of the accumulate-into entry points above (the host side's deterministic training mode,
+ * ops.set_deterministic / WM_DETERMINISTIC=1).  Each wm_<entry>_det computes what wm_<entry> computes - same arguments with
+ * `workspace, workspace_bytes` inserted in front of the sizes, same kernels on the SAME grid - but no workgroup adds into the output:
+ * every workgroup stores its partial sums as one record in the caller-owned workspace, and a finishing kernel (csrc/det.hip.h:
+ * det_finish_kernel) adds the records of each output element in an order that depends on the shapes alone - S lanes per element
+ * (S a power of two <= 64 chosen from the record width and count), lane s adding records s, s + S, ... in ascending order, then the
+ * S lane sums in a butterfly.  The outputs are OVERWRITTEN: they need no zeroing, no zero arena, and a call captured into a HIP
+ * graph holds no accumulator state.  Results are bit-identical run to run and differ from the atomic form's by summation order
+ * only.  Reference counterpart: none (the reference's gradients come from ATen, whose own reductions are not ordered either).
+ *   Workspace: wm_<entry>_det_workspace_bytes(sizes) bytes of uninitialised memory, every byte that is read written first in the
+ *   same call; 0 for an empty or unsupported shape.  Records per output element (= the atomic form's adds per element):
+ *     wm_dwconv3x3_wgrad_det     B x (workgroups per plane) records of 10 C floats [dW taps | db] (zero sums are stored too)
+ *     wm_layernorm2d_bwd_det     min(512, ...) records of 2 C floats [dweight | dbias]; C >= 32 is the two-lanes-per-pixel kernel
+ *     wm_layernorm_tok_bwd_det   min(1024, ...) records of 2 C floats
+ *     wm_linear_wgrad_det        one record of O I floats per workgroup; inside a workgroup the eight waves add their tiles into the
+ *                                LDS record one after the other instead of with LDS atomics
+ *     wm_plane_sums_det          B x (blocks per plane) records of C floats
+ *     wm_scale_add_bwd_det       B x (blocks per plane) records of C floats
+ *     wm_l1_mean_fwd_det         one float per workgroup (at most 1024)
+ *     wm_selscan_bwd_det         behind wm_selscan_bwd's own workspace: the finish kernel's (blocks per channel) x dim records of
+ *                                N + 4 floats [dA | dD, dbias] and, when a group's channels are split over wpg > 1 workgroups
+ *                                (dim / G > 64), wpg slabs each of dB and dC, stored plainly and added in ascending slice order
+ *   Status: as the atomic entry, plus WM_ENULL for a NULL workspace, WM_EWORKSPACE for one that is too small and WM_EALIGN
+ *   (wm_linear_wgrad_det, wm_selscan_bwd_det) for one that is not 16-byte aligned.  An empty problem zeroes the outputs (by a kernel).
+ * -------------------------------------------------------------------------------------------- */
+size_t wm_dwconv3x3_wgrad_det_workspace_bytes(int B, int C, int H, int W);
+int wm_dwconv3x3_wgrad_det(const float* x, const float* gy, float* dW, float* db, void* workspace, size_t workspace_bytes, int B, int C,
+                           int H, int W, void* stream);
+size_t wm_layernorm2d_bwd_det_workspace_bytes(int B, int64_t L, int C);
+int wm_layernorm2d_bwd_det(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight, float* dbias,
+                           void* workspace, size_t workspace_bytes, int B, int64_t L, int C, void* stream);
+size_t wm_layernorm_tok_bwd_det_workspace_bytes(int64_t T, int C);
+int wm_layernorm_tok_bwd_det(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight, float* dbias,
+                             void* workspace, size_t workspace_bytes, int64_t T, int C, void* stream);
+size_t wm_linear_wgrad_det_workspace_bytes(int64_t T, int O, int I);
+int wm_linear_wgrad_det(const float* gy, const float* x, float* dW, void* workspace, size_t workspace_bytes, int64_t T, int O, int I,
+                        void* stream);
+size_t wm_plane_sums_det_workspace_bytes(int B, int C, int H, int W);
+int wm_plane_sums_det(const float* x, float* sums, void* workspace, size_t workspace_bytes, int B, int C, int H, int W, void* stream);
+size_t wm_scale_add_bwd_det_workspace_bytes(int B, int C, int64_t L);
+int wm_scale_add_bwd_det(const float* g, const float* x, const float* scale, float* gx, float* gscale, void* workspace,
+                         size_t workspace_bytes, int B, int C, int64_t L, void* stream);
+size_t wm_l1_mean_fwd_det_workspace_bytes(int64_t n);
+int wm_l1_mean_fwd_det(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, int64_t n, void* stream);
+size_t wm_selscan_bwd_det_workspace_bytes(int batch, int dim, int L, int N, int G);
+int wm_selscan_bwd_det(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm, const float* D,
+                       const float* delta_bias, const float* dy, float* du, float* ddelta, float* dA, float* dB, float* dC, float* dD,
+                       float* dbias, void* workspace, size_t workspace_bytes, int batch, int dim, int L, int N, int G,
+                       int delta_softplus, void* stream);
+
+/* Channel gather with one index per (batch element, output channel) and its gradient (csrc/det.hip.h): the two gathers of the HFE
+ * branch - Matching's matched candidate maps (wavemamba_arch.py:666) and PAConv's cat([x, matched]) (:713) - whose backward in the
+ * reference is ATen's scatter-add (float atomics: the order of two sources of one channel is not fixed).
+ *   wm_channel_gather_fwd   y[b, j, :] = x[b, index[b, j], :]          x (B, C, HW), index (B, M) int32, y (B, M, HW); bit for bit
+ *                           torch.gather.  An index outside [0, C) yields a zero plane (the host cannot check a device index).
+ *   wm_channel_gather_bwd   gx[b, c, :] = sum over j with index[b, j] == c of gy[b, j, :], added in ASCENDING j starting from 0;
+ *                           a channel no index names is zero.  gx (B, C, HW) is overwritten (no zeroing, no atomics): one
+ *                           workgroup per (plane segment, c, b) lists the sources of c and adds their planes, so gy is read once.
+ * fp32, dense; HW = the plane size (H W for NCHW maps, the last axis of (B, C, HW) token maps).  HW % 4 == 0 with 16-byte aligned
+ * planes: 16-byte accesses; otherwise element-wise.  No workspace.  WM_EINVAL: a negative size, or C == 0 with something to gather;
+ * WM_ENULL; WM_EALIGN: a pointer not 4-byte aligned; WM_EUNSUPPORTED: B or the grid's channel axis > 65535, M > 1024 (backward). */
+int wm_channel_gather_fwd(const float* x, const int* index, float* y, int B, int C, int M, int64_t HW, void* stream);
+int wm_channel_gather_bwd(const float* gy, const int* index, float* gx, int B, int C, int M, int64_t HW, void* stream);
 
 /* Host-blocking wait for `event` (a hipEvent_t recorded OUTSIDE any capture) that is legal while a stream of this
  * thread is being captured: hipEventSynchronize under a thread-local relaxed capture mode

@@ -7,6 +7,7 @@
     data.DeviceImageStore / data.PairedPatchBatcher       training batches formed on the device from resident uint8 images
 """
 from . import _lib, ops, registry, trainer, inference, metrics, data   # noqa: F401
+from .ops import set_deterministic, is_deterministic   # noqa: F401
 from .registry import ARCH_REGISTRY, build_network   # noqa: F401
 from .archs import wavemamba_arch           # noqa: F401  (registers 'WaveMamba')
 from .archs.wavemamba_arch import WaveMamba  # noqa: F401

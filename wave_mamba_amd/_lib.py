@@ -93,6 +93,25 @@ SIGNATURES = {
     "wm_event_synchronize_relaxed": (_i, [_p]),
     "wm_zero_arena_register": (_i, [_p, _c.c_size_t]),
     "wm_zero_arena_unregister": (_i, [_p]),
+    # deterministic forms: the atomic entry's arguments with (workspace, workspace_bytes) in front of the sizes
+    "wm_dwconv3x3_wgrad_det_workspace_bytes": (_sz, [_i] * 4),
+    "wm_dwconv3x3_wgrad_det": (_i, [_p] * 4 + [_p, _sz] + [_i] * 4 + [_p]),
+    "wm_layernorm2d_bwd_det_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "wm_layernorm2d_bwd_det": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _p, _sz, _i, _i64, _i, _p]),
+    "wm_layernorm_tok_bwd_det_workspace_bytes": (_sz, [_i64, _i]),
+    "wm_layernorm_tok_bwd_det": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _p, _sz, _i64, _i, _p]),
+    "wm_linear_wgrad_det_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wm_linear_wgrad_det": (_i, [_p, _p, _p, _p, _sz, _i64, _i, _i, _p]),
+    "wm_plane_sums_det_workspace_bytes": (_sz, [_i] * 4),
+    "wm_plane_sums_det": (_i, [_p, _p, _p, _sz, _i, _i, _i, _i, _p]),
+    "wm_scale_add_bwd_det_workspace_bytes": (_sz, [_i, _i, _i64]),
+    "wm_scale_add_bwd_det": (_i, [_p] * 5 + [_p, _sz, _i, _i, _i64, _p]),
+    "wm_l1_mean_fwd_det_workspace_bytes": (_sz, [_i64]),
+    "wm_l1_mean_fwd_det": (_i, [_p, _p, _p, _p, _sz, _i64, _p]),
+    "wm_selscan_bwd_det_workspace_bytes": (_sz, [_i] * 5),
+    "wm_selscan_bwd_det": (_i, [_p] * 15 + [_p, _sz] + [_i] * 6 + [_p]),
+    "wm_channel_gather_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
+    "wm_channel_gather_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
 }
 
 _lib = None

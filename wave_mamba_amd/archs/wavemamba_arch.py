@@ -203,7 +203,10 @@ def _cat_gathered(x, x2=None, x2_index=None):
     if x2 is None:
         return x
     if x2_index is not None:
-        x2 = torch.gather(x2, 1, x2_index.long()[:, :, None, None].expand(-1, -1, x2.shape[2], x2.shape[3]))
+        if x2.is_cuda and _hip_ops.is_deterministic():   # ordered backward instead of ATen's scatter-add
+            x2 = _hip_ops.channel_gather(x2, x2_index)
+        else:
+            x2 = torch.gather(x2, 1, x2_index.long()[:, :, None, None].expand(-1, -1, x2.shape[2], x2.shape[3]))
     return torch.cat([x, x2], dim=1)
 
 
@@ -512,6 +515,8 @@ def nearest_candidate_index(maps, candidates, num_matches):
 def nearest_candidate_maps(maps, candidates, num_matches):
     """The matched candidate maps themselves: gather(candidates, nearest_candidate_index) -> (B, num_matches, HW)."""
     best_idx = nearest_candidate_index(maps, candidates, num_matches)
+    if candidates.is_cuda and _hip_ops.is_deterministic():       # ordered backward instead of ATen's scatter-add
+        return _hip_ops.channel_gather(candidates, best_idx)
     gather_idx = best_idx.long().unsqueeze(-1).expand(-1, -1, candidates.size(2))
     return torch.gather(candidates, 1, gather_idx)
 

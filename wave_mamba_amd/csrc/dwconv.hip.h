@@ -182,7 +182,9 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const TP* __restrict__ x
 // dW[c][i][j] = sum_{b,h,w} gy[b,c,h,w] * x[b,c,h+i-1,w+j-1]   (zero padding),   db[c] = sum gy[b,c,h,w]
 // Same strip walk as the forward (3-row register window of x, 4 columns per thread); 10 per-thread partial
 // sums are reduced over the wave by shuffles and leave through one atomicAdd per wave and value.
-template <bool VEC, int LPR = 64>
+// DET (wm_dwconv3x3_wgrad_det): `dW` is the workspace; the workgroup stores the ten sums of plane (b, c) at
+// part[((b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 10 C + 10 c + i], zeros included (det_finish: fixed-order sum).
+template <bool VEC, int LPR = 64, bool DET = false>
 __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                               float* __restrict__ dW, float* __restrict__ db, int C,
                                                               int H, int W, long long planes, int rows) {
@@ -301,7 +303,9 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
             for (int i = 0; i < 10; ++i) {
                 const int sp = LPR == 64 ? 0 : lane / LPR;
                 const float v = (s_part[0][sp][i] + s_part[1][sp][i]) + (s_part[2][sp][i] + s_part[3][sp][i]);
-                if (v != 0.0f) {
+                if constexpr (DET) {
+                    if (pok) dW[(((plane / C) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (10LL * C) + 10 * c + i] = v;
+                } else if (v != 0.0f) {
                     if (i < 9) atomicAdd(dW + c * 9 + i, v);
                     else if (db) atomicAdd(db + c, v);
                 }

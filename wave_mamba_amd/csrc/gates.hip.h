@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void scale_add_fwd_kernel(const float* __restr
 
 // gx = g * s[c];  gs[c] += sum over the block's elements of g * x (wave shuffle + LDS, then ONE atomic per block: the
 // scale gradients are sums of ~10^6 products of both signs - their order of accumulation is not fixed by ATen either).
-template <bool VEC>
+// DET (wm_scale_add_bwd_det): `gs` is the workspace, part[(b * gridDim.x + blockIdx.x) * C + c] (det_finish: fixed-order sum).
+template <bool VEC, bool DET = false>
 __global__ __launch_bounds__(256) void scale_add_bwd_kernel(const float* __restrict__ g, const float* __restrict__ x,
                                                             const float* __restrict__ s, float* __restrict__ gx,
                                                             float* __restrict__ gs, int C, long long L) {
@@ -128,7 +129,11 @@ __global__ __launch_bounds__(256) void scale_add_bwd_kernel(const float* __restr
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(gs + c, (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+    if (threadIdx.x == 0) {
+        const float v = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        if constexpr (DET) gs[((long long)(blockIdx.y / C) * gridDim.x + blockIdx.x) * C + c] = v;
+        else atomicAdd(gs + c, v);
+    }
 }
 
 }  // namespace wm

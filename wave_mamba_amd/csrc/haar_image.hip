@@ -241,8 +241,27 @@ int wm_l1_mean_fwd(const float* a, const float* b, float* out, int64_t n, void* 
     long long blocks = ((vec ? n / 4 : n) + 256 * 8 - 1) / (256 * 8);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(l1_mean_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, out, (long long)n, 1.0f / (float)n, vec);
+    hipLaunchKernelGGL(l1_mean_fwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a, b, out, (long long)n, 1.0f / (float)n, vec);
     return launch_status();
+}
+size_t wm_l1_mean_fwd_det_workspace_bytes(int64_t n) { return n > 0 ? 1024 * sizeof(float) : 0; }    // one float per workgroup
+int wm_l1_mean_fwd_det(const float* a, const float* b, float* out, void* workspace, size_t workspace_bytes, int64_t n, void* stream) {
+    if (n < 0) return WM_EINVAL;
+    if (!out) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        const hipError_t e = zero_out(out, sizeof(float), st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!a || !b || !workspace) return WM_ENULL;
+    if (workspace_bytes < wm_l1_mean_fwd_det_workspace_bytes(n)) return WM_EWORKSPACE;
+    const int vec = (n % 4 == 0) && aligned16(a) && aligned16(b) ? 1 : 0;
+    long long blocks = ((vec ? n / 4 : n) + 256 * 8 - 1) / (256 * 8);
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(l1_mean_fwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a, b, part, (long long)n, 1.0f / (float)n, vec);
+    return det_finish(part, blocks, 1, DetOut{out, nullptr, nullptr, kDetSplit, 1, 0, 0}, st);
 }
 int wm_l1_mean_bwd(const float* a, const float* b, const float* gout, float* ga, int64_t n, void* stream) {
     if (n < 0) return WM_EINVAL;

@@ -98,6 +98,8 @@ __global__ __launch_bounds__(256) void chansum3_kernel(const float* __restrict__
 
 // sums[c] += sum over the batch and the plane of x[b, c]: bias gradients of the convolutions in training (ATen's
 // generic reduce kernel spent 41 us per call on it).  grid (blocks per plane, B * C), block (256)
+// DET (wm_plane_sums_det): `sums` is the workspace, part[(b * gridDim.x + blockIdx.x) * C + c] (det_finish: fixed-order sum).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void plane_sums_kernel(const float* __restrict__ x, float* __restrict__ sums, int C,
                                                          long long HW, bool vec) {
     const long long plane = blockIdx.y;
@@ -117,7 +119,11 @@ __global__ __launch_bounds__(256) void plane_sums_kernel(const float* __restrict
     __shared__ float s_w[4];
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(sums + (plane % C), (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]));
+    if (threadIdx.x == 0) {
+        const float v = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+        if constexpr (DET) sums[((plane / C) * gridDim.x + blockIdx.x) * C + (plane % C)] = v;
+        else atomicAdd(sums + (plane % C), v);
+    }
 }
 
 // grid (B), block (64): block partials of the plane sums (B, C, bpp) -> band weights w (B, 3, C).  Wdu (d, C), prelu (1), Wfc (3, C, d); no biases

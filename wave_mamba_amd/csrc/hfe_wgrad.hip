@@ -135,6 +135,39 @@ int wm_conv2d_wgrad(const float* gy, const float* x, float* dW, float* db, void*
     return launch_status();
 }
 
+// blocks per plane of the plane-sum launch
+static long long plane_sums_bpp(long long planes, long long HW) {
+    long long bpp = (HW / 4 + 256 * 8 - 1) / (256 * 8);
+    const long long cap = (256 * 16 + planes - 1) / planes;
+    if (bpp > cap) bpp = cap;
+    return bpp < 1 ? 1 : bpp;
+}
+
+size_t wm_plane_sums_det_workspace_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)B * plane_sums_bpp((long long)B * C, (long long)H * W) * C * sizeof(float);
+}
+
+int wm_plane_sums_det(const float* x, float* sums, void* workspace, size_t workspace_bytes, int B, int C, int H, int W, void* stream) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (C == 0) return WM_OK;
+    if (!sums) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const long long HW = (long long)H * W, planes = (long long)B * C;
+    if (planes == 0 || HW == 0) {
+        const hipError_t e = zero_out(sums, (size_t)C * sizeof(float), st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!x || !workspace) return WM_ENULL;
+    if (planes > 65535) return WM_EUNSUPPORTED;
+    if (workspace_bytes < wm_plane_sums_det_workspace_bytes(B, C, H, W)) return WM_EWORKSPACE;
+    const bool vec = (HW % 4 == 0) && aligned16(x);
+    const long long bpp = plane_sums_bpp(planes, HW);
+    float* part = (float*)workspace;
+    hipLaunchKernelGGL(plane_sums_kernel<true>, dim3((unsigned)bpp, (unsigned)planes), dim3(256), 0, st, x, part, C, HW, vec);
+    return det_finish(part, (long long)B * bpp, C, DetOut{sums, nullptr, nullptr, kDetSplit, C, 0, 0}, st);
+}
+
 int wm_plane_sums(const float* x, float* sums, int B, int C, int H, int W, void* stream) {
     if (B < 0 || C < 0 || H < 0 || W < 0) return WM_EINVAL;
     if (C == 0) return WM_OK;
@@ -147,11 +180,8 @@ int wm_plane_sums(const float* x, float* sums, int B, int C, int H, int W, void*
     if (!x) return WM_ENULL;
     if (planes > 65535) return WM_EUNSUPPORTED;
     const bool vec = (HW % 4 == 0) && aligned16(x);
-    long long bpp = (HW / 4 + 256 * 8 - 1) / (256 * 8);
-    const long long cap = (256 * 16 + planes - 1) / planes;
-    if (bpp > cap) bpp = cap;
-    if (bpp < 1) bpp = 1;
-    hipLaunchKernelGGL(plane_sums_kernel, dim3((unsigned)bpp, (unsigned)planes), dim3(256), 0, st, x, sums, C, HW, vec);
+    const long long bpp = plane_sums_bpp(planes, HW);
+    hipLaunchKernelGGL(plane_sums_kernel<false>, dim3((unsigned)bpp, (unsigned)planes), dim3(256), 0, st, x, sums, C, HW, vec);
     return launch_status();
 }
 

@@ -64,6 +64,16 @@ WM_HIDDEN hipError_t zero_out(void* p, size_t bytes, hipStream_t st);
 // two small gradient buffers: one launch when the caller allocated them back to back
 WM_HIDDEN hipError_t zero_pair(float* a, size_t na, float* b, size_t nb, hipStream_t st);
 
+// Deterministic forms (wm_*_det): the kernels store one partial per workgroup, part[j * K + k] for workgroup slot j < nblk and value
+// k < K, and det_finish (det.hip) adds the nblk partials of every k in an order that depends on (nblk, K) alone and OVERWRITES the
+// outputs.  Where value k goes:
+//   kDetSplit   k < a -> o0[k], else o1[k - a] (o1 may be NULL)                                  (dweight | dbias, sums, a scalar)
+//   kDetDw      k = 10 c + i: i < 9 -> o0[9 c + i], i == 9 -> o1[c] (o1 may be NULL)             (depth-wise dW | db)
+//   kDetScan    k = a d + t (a = record length): t < b -> o0[b d + t], t == c -> o1[d], t == c + 1 -> o2[d] (o1, o2 may be NULL)
+enum { kDetSplit = 0, kDetDw = 1, kDetScan = 2 };
+struct DetOut { float *o0, *o1, *o2; int mode, a, b, c; };
+WM_HIDDEN int det_finish(const float* part, long long nblk, long long K, const DetOut& out, hipStream_t st);
+
 // > 64 KB of dynamic LDS is an opt-in per kernel function AND per device: one flag per (instantiation, device).
 // `flags` is the caller's function-local static array; returns WM_OK or WM_EHIP.
 WM_HIDDEN int lds_optin(const void* fn, int bytes, bool (&flags)[64]);

@@ -317,6 +317,77 @@ int wm_dwconv3x3_wgrad(const float* x, const float* gy, float* dW, float* db, in
     return launch_status();
 }
 
+size_t wm_dwconv3x3_wgrad_det_workspace_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    // (the widest grid of the two access forms: the workspace does not depend on the pointers' alignment)
+    const DwGeometry gv = dw_geometry(H, W, (long long)B * C, W % 4 == 0, false), gs = dw_geometry(H, W, (long long)B * C, false, false);
+    const size_t nv = (size_t)gv.grid.x * gv.grid.y, ns = (size_t)gs.grid.x * gs.grid.y;
+    return (size_t)B * (nv > ns ? nv : ns) * 10 * C * sizeof(float);
+}
+
+int wm_dwconv3x3_wgrad_det(const float* x, const float* gy, float* dW, float* db, void* workspace, size_t workspace_bytes, int B, int C,
+                           int H, int W, void* stream) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (C == 0) return WM_OK;
+    if (!dW) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const long long planes = (long long)B * C;
+    if (planes == 0 || H == 0 || W == 0) {
+        const hipError_t e = zero_pair(dW, (size_t)C * 9, db, (size_t)C, st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!x || !gy || !workspace) return WM_ENULL;
+    if (workspace_bytes < wm_dwconv3x3_wgrad_det_workspace_bytes(B, C, H, W)) return WM_EWORKSPACE;
+    const DwGeometry g = dw_geometry(H, W, planes, (W % 4 == 0) && aligned16(x) && aligned16(gy), false);
+    float* part = (float*)workspace;
+    with_dw_lanes(g, [&](auto vec, auto lpr) {
+        hipLaunchKernelGGL((dwconv3x3_wgrad_kernel<vec(), lpr(), true>), g.grid, g.block, 0, st, x, gy, part, (float*)nullptr, C, H, W,
+                           planes, g.rows);
+    });
+    return det_finish(part, (long long)B * g.grid.x * g.grid.y, 10LL * C, DetOut{dW, db, nullptr, kDetDw, 0, 0, 0}, st);
+}
+
+// workgroups of the two LayerNorm backward launches (the atomic and the deterministic form share them)
+static long long ln2d_bwd_blocks(long long total, int C) {
+    const int tpp = C >= 32 ? 2 : 1;                     // threads per pixel (layernorm2d_bwd_pair_kernel)
+    long long blocks = (total * tpp + 255) / 256;
+    return blocks > 512 ? 512 : blocks;                  // grid-stride: few blocks -> few atomics per channel
+}
+static long long ln_tok_bwd_blocks(long long T, int C) {
+    const int tpb = 256 / (C / 4);
+    long long blocks = (T + tpb - 1) / tpb;
+    return blocks > 1024 ? 1024 : blocks;                // grid-stride: few blocks -> few atomics per channel
+}
+
+size_t wm_layernorm2d_bwd_det_workspace_bytes(int B, int64_t L, int C) {
+    if (B <= 0 || L <= 0 || (C != 8 && C != 16 && C != 32 && C != 64)) return 0;
+    return (size_t)ln2d_bwd_blocks((long long)B * L, C) * 2 * C * sizeof(float);
+}
+
+int wm_layernorm2d_bwd_det(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight, float* dbias,
+                           void* workspace, size_t workspace_bytes, int B, int64_t L, int C, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (C != 8 && C != 16 && C != 32 && C != 64) return WM_EUNSUPPORTED;
+    if (!dweight || !dbias) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)B * L;
+    if (total == 0) {
+        const hipError_t e = zero_pair(dweight, (size_t)C, dbias, (size_t)C, st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!x || !weight || !gy || !gx || !workspace) return WM_ENULL;
+    if (workspace_bytes < wm_layernorm2d_bwd_det_workspace_bytes(B, L, C)) return WM_EWORKSPACE;
+    const long long blocks = ln2d_bwd_blocks(total, C);
+    const dim3 grid((unsigned)blocks), block(256);
+    float* part = (float*)workspace;
+    with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
+        constexpr int CC = c();
+        if constexpr (CC >= 32) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<CC, true>), grid, block, 0, st, x, weight, gy, eps, gx, part, (float*)nullptr, B, (long long)L);
+        else hipLaunchKernelGGL((layernorm2d_bwd_kernel<CC, true>), grid, block, 0, st, x, weight, gy, eps, gx, part, (float*)nullptr, B, (long long)L);
+    });
+    return det_finish(part, blocks, 2LL * C, DetOut{dweight, dbias, nullptr, kDetSplit, C, 0, 0}, st);
+}
+
 int wm_layernorm2d_bwd(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight,
                        float* dbias, int B, int64_t L, int C, void* stream) {
     if (B < 0 || L < 0) return WM_EINVAL;
@@ -328,10 +399,7 @@ int wm_layernorm2d_bwd(const float* x, const float* weight, const float* gy, flo
     const long long total = (long long)B * L;
     if (total == 0) return WM_OK;
     if (!x || !weight || !gy || !gx) return WM_ENULL;
-    const int tpp = C >= 32 ? 2 : 1;                     // threads per pixel (layernorm2d_bwd_pair_kernel)
-    long long blocks = (total * tpp + 255) / 256;
-    if (blocks > 512) blocks = 512;                      // grid-stride: few blocks -> few atomics per channel
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid((unsigned)ln2d_bwd_blocks(total, C)), block(256);
     with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
         constexpr int CC = c();
         if constexpr (CC >= 32) hipLaunchKernelGGL((layernorm2d_bwd_pair_kernel<CC>), grid, block, 0, st, x, weight, gy, eps, gx, dweight, dbias, B, (long long)L);
@@ -370,15 +438,40 @@ int wm_layernorm_tok_bwd(const float* x, const float* weight, const float* gy, f
     if (T == 0) return WM_OK;
     if (!x || !weight || !gy || !gx) return WM_ENULL;
     if (!aligned16(x) || !aligned16(gy) || !aligned16(gx) || !aligned16(weight)) return WM_EALIGN;
-    const int tpb = 256 / (C / 4);
-    long long blocks = (T + tpb - 1) / tpb;
-    if (blocks > 1024) blocks = 1024;                    // grid-stride: few blocks -> few atomics per channel
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid((unsigned)ln_tok_bwd_blocks(T, C)), block(256);
     with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
         hipLaunchKernelGGL((layernorm_tok_bwd_kernel<c()>), grid, block, 0, st, (const float4*)x, (const float4*)weight, (const float4*)gy, eps,
                            (float4*)gx, dweight, dbias, (long long)T);
     });
     return launch_status();
+}
+
+size_t wm_layernorm_tok_bwd_det_workspace_bytes(int64_t T, int C) {
+    if (T <= 0 || (C != 8 && C != 16 && C != 32 && C != 64)) return 0;
+    return (size_t)ln_tok_bwd_blocks(T, C) * 2 * C * sizeof(float);
+}
+
+int wm_layernorm_tok_bwd_det(const float* x, const float* weight, const float* gy, float eps, float* gx, float* dweight, float* dbias,
+                             void* workspace, size_t workspace_bytes, int64_t T, int C, void* stream) {
+    if (T < 0) return WM_EINVAL;
+    if (C != 8 && C != 16 && C != 32 && C != 64) return WM_EUNSUPPORTED;
+    if (!dweight || !dbias) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    if (T == 0) {
+        const hipError_t e = zero_pair(dweight, (size_t)C, dbias, (size_t)C, st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!x || !weight || !gy || !gx || !workspace) return WM_ENULL;
+    if (!aligned16(x) || !aligned16(gy) || !aligned16(gx) || !aligned16(weight)) return WM_EALIGN;
+    if (workspace_bytes < wm_layernorm_tok_bwd_det_workspace_bytes(T, C)) return WM_EWORKSPACE;
+    const long long blocks = ln_tok_bwd_blocks(T, C);
+    const dim3 grid((unsigned)blocks), block(256);
+    float* part = (float*)workspace;
+    with_channels<64 | 32 | 16 | 8>(C, [&](auto c) {
+        hipLaunchKernelGGL((layernorm_tok_bwd_kernel<c(), true>), grid, block, 0, st, (const float4*)x, (const float4*)weight, (const float4*)gy,
+                           eps, (float4*)gx, part, (float*)nullptr, (long long)T);
+    });
+    return det_finish(part, blocks, 2LL * C, DetOut{dweight, dbias, nullptr, kDetSplit, C, 0, 0}, st);
 }
 
 // act: 1 = SiLU, 2 = GELU (erf).  a / b / out (and g / ga / gb) are (B, per_b) with batch strides in elements.
@@ -432,6 +525,41 @@ int wm_scale_add_fwd(const float* x, const float* scale, const float* o, float* 
     return launch_status();
 }
 
+// blocks per plane of the scale_add backward: <= 8 (scale_add_bwd_kernel), >= ~2048 in all if the map allows
+static long long scale_add_bwd_bpp(int B, int C, int64_t L) {
+    long long bpp = (L + 1023) / 1024;
+    const long long want = (2048 + (long long)B * C - 1) / ((long long)B * C);
+    const long long cap = want > 8 ? want : 8;
+    return bpp > cap ? cap : bpp;
+}
+
+size_t wm_scale_add_bwd_det_workspace_bytes(int B, int C, int64_t L) {
+    if (B <= 0 || C <= 0 || L <= 0) return 0;
+    return (size_t)B * scale_add_bwd_bpp(B, C, L) * C * sizeof(float);
+}
+
+int wm_scale_add_bwd_det(const float* g, const float* x, const float* scale, float* gx, float* gscale, void* workspace,
+                         size_t workspace_bytes, int B, int C, int64_t L, void* stream) {
+    if (B < 0 || C < 0 || L < 0) return WM_EINVAL;
+    if (C == 0) return WM_OK;
+    if (!gscale) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0 || L == 0) {
+        const hipError_t e = zero_out(gscale, (size_t)C * sizeof(float), st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!g || !x || !scale || !gx || !workspace) return WM_ENULL;
+    if ((long long)B * C > 65535) return WM_EUNSUPPORTED;
+    if (workspace_bytes < wm_scale_add_bwd_det_workspace_bytes(B, C, L)) return WM_EWORKSPACE;
+    const bool vec = L % 4 == 0 && aligned16(g) && aligned16(x) && aligned16(gx);
+    const long long bpp = scale_add_bwd_bpp(B, C, L);
+    const dim3 grid((unsigned)bpp, (unsigned)(B * C)), block(256);
+    float* part = (float*)workspace;
+    if (vec) hipLaunchKernelGGL((scale_add_bwd_kernel<true, true>), grid, block, 0, st, g, x, scale, gx, part, C, (long long)L);
+    else hipLaunchKernelGGL((scale_add_bwd_kernel<false, true>), grid, block, 0, st, g, x, scale, gx, part, C, (long long)L);
+    return det_finish(part, (long long)B * bpp, C, DetOut{gscale, nullptr, nullptr, kDetSplit, C, 0, 0}, st);
+}
+
 int wm_scale_add_bwd(const float* g, const float* x, const float* scale, float* gx, float* gscale, int B, int C, int64_t L,
                      void* stream) {
     if (B < 0 || C < 0 || L < 0) return WM_EINVAL;
@@ -444,11 +572,7 @@ int wm_scale_add_bwd(const float* g, const float* x, const float* scale, float* 
     if (!g || !x || !scale || !gx) return WM_ENULL;
     if ((long long)B * C > 65535) return WM_EUNSUPPORTED;
     const bool vec = L % 4 == 0 && aligned16(g) && aligned16(x) && aligned16(gx);
-    long long bpp = (L + 1023) / 1024;                       // blocks per plane: <= 8 (scale_add_bwd_kernel), >= ~2048 in all if the map allows
-    const long long want = (2048 + (long long)B * C - 1) / ((long long)B * C);
-    const long long cap = want > 8 ? want : 8;
-    if (bpp > cap) bpp = cap;
-    const dim3 grid((unsigned)bpp, (unsigned)(B * C)), block(256);
+    const dim3 grid((unsigned)scale_add_bwd_bpp(B, C, L), (unsigned)(B * C)), block(256);
     if (vec) hipLaunchKernelGGL(scale_add_bwd_kernel<true>, grid, block, 0, st, g, x, scale, gx, gscale, C, (long long)L);
     else hipLaunchKernelGGL(scale_add_bwd_kernel<false>, grid, block, 0, st, g, x, scale, gx, gscale, C, (long long)L);
     return launch_status();

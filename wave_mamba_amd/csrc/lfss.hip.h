@@ -189,10 +189,12 @@ __global__ __launch_bounds__(256) void layernorm2d_kernel(const float* __restric
 }
 
 // ---- LayerNorm2d backward (reference LayerNormFunction.backward, :545-557) --------------------------------
+// DET (the wm_layernorm*_bwd_det entry points, all three kernels): workgroup j stores its 2 C sums as the record part[j * 2 C ..] in
+// the workspace passed as `dw` instead of adding them to dw / db; det_finish adds the records in a fixed order.
 //   g = gy * w ;  gx = rstd * (g - yhat * mean_c(g * yhat) - mean_c(g)) ;  dw[c] = sum gy*yhat ;  db[c] = sum gy
 // one thread = one pixel (mean / rstd / yhat recomputed from x); dw / db partials live in registers over a
 // grid-stride loop and leave through a wave shuffle reduction + one atomicAdd per wave and channel.
-template <int C>
+template <int C, bool DET = false>
 __global__ __launch_bounds__(256) void layernorm2d_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ gy, float eps,
                                                               float* __restrict__ gx, float* __restrict__ dw,
@@ -239,7 +241,8 @@ __global__ __launch_bounds__(256) void layernorm2d_bwd_kernel(const float* __res
     __syncthreads();
     if (threadIdx.x < 2 * C) {
         const float t = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
-        atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
+        if constexpr (DET) dw[(long long)blockIdx.x * (2 * C) + threadIdx.x] = t;       // dw = the workspace: record [dweight | dbias]
+        else atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
     }
 }
 
@@ -250,7 +253,7 @@ __global__ __launch_bounds__(256) void layernorm2d_bwd_kernel(const float* __res
 // for C = 64 streamed the channels three times with only the parameter-gradient partials in registers (370 us for a 134-MB map:
 // 800 MB of cache re-reads); the one-lane-per-pixel form above needs 4 C registers per thread.  Twice the threads per pixel also
 // fills the chip on the 64 x 64 maps of BASELINE config 3 (32,768 pixels).
-template <int C>
+template <int C, bool DET = false>
 __global__ __launch_bounds__(256) void layernorm2d_bwd_pair_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                    const float* __restrict__ gy, float eps,
                                                                    float* __restrict__ gx, float* __restrict__ dw,
@@ -304,7 +307,8 @@ __global__ __launch_bounds__(256) void layernorm2d_bwd_pair_kernel(const float* 
     __syncthreads();
     if (threadIdx.x < 2 * C) {
         const float t = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
-        atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
+        if constexpr (DET) dw[(long long)blockIdx.x * (2 * C) + threadIdx.x] = t;       // dw = the workspace: record [dweight | dbias]
+        else atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
     }
 }
 
@@ -337,7 +341,7 @@ __global__ __launch_bounds__(256) void layernorm_tok_kernel(const float4* __rest
                                      fmaf(d.z * rstd, wv.z, bv.z), fmaf(d.w * rstd, wv.w, bv.w));
     }
 }
-template <int C>
+template <int C, bool DET = false>
 __global__ __launch_bounds__(256) void layernorm_tok_bwd_kernel(const float4* __restrict__ x, const float4* __restrict__ w,
                                                                 const float4* __restrict__ gy, float eps,
                                                                 float4* __restrict__ gx, float* __restrict__ dw,
@@ -376,7 +380,8 @@ __global__ __launch_bounds__(256) void layernorm_tok_bwd_kernel(const float4* __
     __syncthreads();
     if (threadIdx.x < 2 * C) {
         const float t = (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-        atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
+        if constexpr (DET) dw[(long long)blockIdx.x * (2 * C) + threadIdx.x] = t;       // dw = the workspace: record [dweight | dbias]
+        else atomicAdd((threadIdx.x < C ? dw : db) + (threadIdx.x % C), t);
     }
 }
 

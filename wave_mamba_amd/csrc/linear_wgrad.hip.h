@@ -67,7 +67,9 @@ template <int NT> __device__ __forceinline__ int lw_channel(int a, int r) {
     constexpr int V = LwVec<NT>::V;
     return (a / V) * 16 * V + V * r + (a % V);
 }
-template <int OT, int IT>
+// DET (wm_linear_wgrad_det): the waves add their tiles into the LDS record one after the other (wave 0 first), and the workgroup
+// stores the record at part[blockIdx.x * O I ..] in the workspace passed as `dW` (det_finish: fixed-order sum).
+template <int OT, int IT, bool DET = false>
 __global__ __launch_bounds__(64 * kLwWaves) void linear_wgrad_kernel(const float* __restrict__ gy, const float* __restrict__ x,
                                                                      float* __restrict__ dW, long long T, long long slice) {
     constexpr int O = 16 * OT, I = 16 * IT;
@@ -95,6 +97,23 @@ __global__ __launch_bounds__(64 * kLwWaves) void linear_wgrad_kernel(const float
             for (int b = 0; b < IT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[a], xa[b], acc[a][b], 0, 0, 0);
     }
     // D layout: lane holds tile rows 4 kq .. 4 kq + 3 (o side) of tile column r (i side)
+    if constexpr (DET) {
+        // (for one (a, b, q) the 64 lanes of a wave own 64 different elements: plain read-modify-write inside a wave's turn)
+        for (int turn = 0; turn < kLwWaves; ++turn) {
+            if (wv == turn) {
+#pragma unroll
+                for (int a = 0; a < OT; ++a)
+#pragma unroll
+                    for (int b = 0; b < IT; ++b)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            s_part[lw_channel<OT>(a, 4 * kq + q) * I + lw_channel<IT>(b, r)] += acc[a][b][q];
+            }
+            __syncthreads();
+        }
+        for (int e = threadIdx.x; e < O * I; e += 64 * kLwWaves) dW[(long long)blockIdx.x * (O * I) + e] = s_part[e];
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < OT; ++a)
 #pragma unroll

@@ -13,6 +13,8 @@
 
 namespace wm {
 
+// DET (wm_l1_mean_fwd_det): `out` is the workspace and workgroup j stores its share at out[j] (det_finish adds them in a fixed order).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void l1_mean_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                           float* __restrict__ out, long long n, float inv_n, int vec) {
     const long long stride = (long long)gridDim.x * 256;
@@ -32,7 +34,10 @@ __global__ __launch_bounds__(256) void l1_mean_fwd_kernel(const float* __restric
     __shared__ float part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, ((part[0] + part[1]) + (part[2] + part[3])) * inv_n);
+    if (threadIdx.x == 0) {
+        const float v = ((part[0] + part[1]) + (part[2] + part[3])) * inv_n;
+        if constexpr (DET) out[blockIdx.x] = v; else atomicAdd(out, v);
+    }
 }
 
 // ga = gout * sign(a - b) / n  (torch: l1_loss_backward; sign(0) = 0)

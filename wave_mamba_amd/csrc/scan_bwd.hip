@@ -97,9 +97,10 @@ static void bwd_bind_workspace(ScanBwdArgs& a, const BwdPlan& pl, char* w, float
     a.nchunks = pl.nchunks; a.cpb = pl.cpb; a.nblocks = pl.nblocks;
 }
 
+// det_ws: NULL, or (wm_selscan_bwd_det) the room for the finish kernel's records - dA / dD / dbias are then written by det_finish
 template <int NP, bool VEC>
 static int bwd_launch(const ScanBwdArgs& a0, const BwdPlan& pl, float* seg, float* dA, float* dD, float* dbias,
-                      hipStream_t st) {
+                      hipStream_t st, float* det_ws = nullptr) {
     ScanBwdArgs a = a0;
     const dim3 grid((unsigned)pl.nblocks, (unsigned)pl.rows), block(64);
     ProfScope ps(12, st);
@@ -108,11 +109,18 @@ static int bwd_launch(const ScanBwdArgs& a0, const BwdPlan& pl, float* seg, floa
         if (pl.nblocks > 1) bwd_launch_carry(a, pl, seg, st);
     }
     hipLaunchKernelGGL((selscan_bwd_chunk_kernel<NP, VEC>), grid, block, 0, st, a);
+    if (det_ws) {
+        const int ysplit = bwd_finish_split(pl.nblocks, NP + kPartPad);
+        hipLaunchKernelGGL(selscan_bwd_finish_kernel<true>, dim3((unsigned)a.dim, (unsigned)ysplit), dim3(256), 0, st,
+                           (const float*)a.part, det_ws, (float*)nullptr, (float*)nullptr, a.batch, a.dim, a.N, NP + kPartPad,
+                           pl.nblocks, NP);
+        return det_finish(det_ws, ysplit, (long long)a.dim * (NP + kPartPad), DetOut{dA, dD, dbias, kDetScan, NP + kPartPad, a.N, NP}, st);
+    }
     zero_async(dA, (size_t)a.dim * a.N * sizeof(float), st);
     if (dD) zero_async(dD, (size_t)a.dim * sizeof(float), st);
     if (dbias) zero_async(dbias, (size_t)a.dim * sizeof(float), st);
     const int ysplit = bwd_finish_split(pl.nblocks, NP + kPartPad);
-    hipLaunchKernelGGL(selscan_bwd_finish_kernel, dim3((unsigned)a.dim, (unsigned)ysplit), dim3(256), 0, st,
+    hipLaunchKernelGGL(selscan_bwd_finish_kernel<false>, dim3((unsigned)a.dim, (unsigned)ysplit), dim3(256), 0, st,
                        (const float*)a.part, dA, dD, dbias, a.batch, a.dim, a.N, NP + kPartPad, pl.nblocks, NP);
     return launch_status();
 }
@@ -241,14 +249,21 @@ static int core_bwd_v2(const CoreBwdPlan2& pl, const float* x, const float* x_pr
     return launch_status();
 }
 
-template <int OT, int IT>
-static void linear_wgrad_launch(const float* gy, const float* x, float* dW, long long T, hipStream_t st) {
+// waves of a linear_wgrad launch (a multiple of kLwWaves) and the tokens each takes
+static long long linear_wgrad_waves(long long T, long long& slice) {
     long long waves = (T + 511) / 512;                                  // >= 512 tokens per wave
     if (waves > 4096) waves = 4096;
+    if (waves < 1) waves = 1;
     waves = ((waves + kLwWaves - 1) / kLwWaves) * kLwWaves;
-    long long slice = (T + waves - 1) / waves;
+    slice = (T + waves - 1) / waves;
     slice = ((slice + 3) / 4) * 4;
-    hipLaunchKernelGGL((linear_wgrad_kernel<OT, IT>), dim3((unsigned)(waves / kLwWaves)), dim3(64 * kLwWaves), 0,
+    return waves;
+}
+template <int OT, int IT, bool DET = false>
+static void linear_wgrad_launch(const float* gy, const float* x, float* dW, long long T, hipStream_t st) {
+    long long slice;
+    const long long waves = linear_wgrad_waves(T, slice);
+    hipLaunchKernelGGL((linear_wgrad_kernel<OT, IT, DET>), dim3((unsigned)(waves / kLwWaves)), dim3(64 * kLwWaves), 0,
                        st, gy, x, dW, T, slice);
 }
 
@@ -264,18 +279,31 @@ size_t wm_selscan_bwd_workspace_bytes(int batch, int dim, int L, int N, int G) {
     return pl.total;
 }
 
-int wm_selscan_bwd(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm,
-                   const float* D, const float* delta_bias, const float* dy, float* du, float* ddelta,
-                   float* dA, float* dB, float* dC, float* dD, float* dbias, void* workspace,
-                   size_t workspace_bytes, int batch, int dim, int L, int N, int G, int delta_softplus,
-                   void* stream) {
+// the deterministic form's room behind the plan's own workspace: the finish kernel's records [ysplit][dim][NP + pad], then (wpg > 1)
+// wpg slabs each of dB and dC
+struct BwdDetPlan { size_t fin_bytes, slab_elems, total; int ysplit; };
+static void bwd_det_plan(BwdDetPlan& dp, const BwdPlan& pl, int batch, int dim, int L, int N, int G) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    dp.ysplit = bwd_finish_split(pl.nblocks, pl.NP + kPartPad);
+    dp.fin_bytes = up((size_t)dp.ysplit * dim * (pl.NP + kPartPad) * sizeof(float));
+    dp.slab_elems = pl.wpg > 1 ? (size_t)batch * G * N * L : 0;
+    dp.total = up(pl.total) + dp.fin_bytes + up(2 * (size_t)pl.wpg * dp.slab_elems * sizeof(float));
+}
+
+static int selscan_bwd_entry(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm,
+                             const float* D, const float* delta_bias, const float* dy, float* du, float* ddelta,
+                             float* dA, float* dB, float* dC, float* dD, float* dbias, void* workspace,
+                             size_t workspace_bytes, int batch, int dim, int L, int N, int G, int delta_softplus,
+                             void* stream, bool det) {
     if (batch == 0 || dim == 0 || L == 0) return (batch < 0 || dim < 0 || L < 0) ? WM_EINVAL : WM_OK;
     BwdPlan pl;
     int rc = bwd_plan(pl, batch, dim, L, N, G);
     if (rc) return rc;
     if (!u || !delta || !A || !Bm || !Cm || !dy || !du || !ddelta || !dA || !dB || !dC) return WM_ENULL;
     if (!workspace) return WM_ENULL;
-    if (workspace_bytes < pl.total) return WM_EWORKSPACE;
+    BwdDetPlan dp{};
+    if (det) bwd_det_plan(dp, pl, batch, dim, L, N, G);
+    if (workspace_bytes < (det ? dp.total : pl.total)) return WM_EWORKSPACE;
     if (!aligned16(workspace)) return WM_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     ScanBwdArgs a;
@@ -284,7 +312,15 @@ int wm_selscan_bwd(const float* u, const float* delta, const float* A, const flo
     float* seg = nullptr;
     bwd_bind_workspace(a, pl, (char*)workspace, seg);
     a.batch = batch; a.dim = dim; a.L = L; a.N = N; a.G = G; a.dpg = dim / G; a.wpg = pl.wpg;
-    a.softplus = delta_softplus ? 1 : 0; a.atomic_bc = pl.wpg > 1 ? 1 : 0;
+    a.softplus = delta_softplus ? 1 : 0; a.atomic_bc = pl.wpg > 1 && !det ? 1 : 0;
+    a.bc_slab = 0;
+    float* fin = nullptr;
+    float* slabs = nullptr;
+    if (det) {
+        fin = (float*)((char*)workspace + (pl.total + 255) / 256 * 256);
+        slabs = (float*)((char*)fin + dp.fin_bytes);
+        if (pl.wpg > 1) { a.dB = slabs; a.dC = slabs + (size_t)pl.wpg * dp.slab_elems; a.bc_slab = (long long)dp.slab_elems; }
+    }
     if (a.atomic_bc) {
         const size_t nb = (size_t)batch * G * N * L * sizeof(float);
         hipError_t e = zero_async(dB, nb, st);
@@ -293,9 +329,44 @@ int wm_selscan_bwd(const float* u, const float* delta, const float* A, const flo
     }
     const bool vec = (L % 4 == 0) && aligned16(u) && aligned16(delta) && aligned16(Bm) && aligned16(Cm) &&
                      aligned16(dy) && aligned16(du) && aligned16(ddelta) && aligned16(dB) && aligned16(dC);
-    if (pl.NP == 16) return vec ? bwd_launch<16, true>(a, pl, seg, dA, dD, dbias, st)
-                                : bwd_launch<16, false>(a, pl, seg, dA, dD, dbias, st);
-    return vec ? bwd_launch<32, true>(a, pl, seg, dA, dD, dbias, st) : bwd_launch<32, false>(a, pl, seg, dA, dD, dbias, st);
+    if (pl.NP == 16) rc = vec ? bwd_launch<16, true>(a, pl, seg, dA, dD, dbias, st, fin)
+                              : bwd_launch<16, false>(a, pl, seg, dA, dD, dbias, st, fin);
+    else rc = vec ? bwd_launch<32, true>(a, pl, seg, dA, dD, dbias, st, fin) : bwd_launch<32, false>(a, pl, seg, dA, dD, dbias, st, fin);
+    if (rc || !det || pl.wpg <= 1) return rc;
+    // dB, dC = the wpg slabs added in ascending channel-slice order
+    const long long n = (long long)dp.slab_elems;
+    const int sv = vec ? 1 : 0;                                   // (L % 4 == 0: n % 4 == 0 and every slab starts 16-byte aligned)
+    long long blocks = ((sv ? n / 4 : n) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(det_slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)a.dB, dB, n, pl.wpg, sv);
+    hipLaunchKernelGGL(det_slab_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)a.dC, dC, n, pl.wpg, sv);
+    return launch_status();
+}
+
+int wm_selscan_bwd(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm,
+                   const float* D, const float* delta_bias, const float* dy, float* du, float* ddelta,
+                   float* dA, float* dB, float* dC, float* dD, float* dbias, void* workspace,
+                   size_t workspace_bytes, int batch, int dim, int L, int N, int G, int delta_softplus,
+                   void* stream) {
+    return selscan_bwd_entry(u, delta, A, Bm, Cm, D, delta_bias, dy, du, ddelta, dA, dB, dC, dD, dbias, workspace, workspace_bytes,
+                             batch, dim, L, N, G, delta_softplus, stream, false);
+}
+
+size_t wm_selscan_bwd_det_workspace_bytes(int batch, int dim, int L, int N, int G) {
+    BwdPlan pl;
+    if (bwd_plan(pl, batch, dim, L, N, G) != WM_OK) return 0;
+    BwdDetPlan dp;
+    bwd_det_plan(dp, pl, batch, dim, L, N, G);
+    return dp.total;
+}
+
+int wm_selscan_bwd_det(const float* u, const float* delta, const float* A, const float* Bm, const float* Cm,
+                       const float* D, const float* delta_bias, const float* dy, float* du, float* ddelta,
+                       float* dA, float* dB, float* dC, float* dD, float* dbias, void* workspace,
+                       size_t workspace_bytes, int batch, int dim, int L, int N, int G, int delta_softplus,
+                       void* stream) {
+    return selscan_bwd_entry(u, delta, A, Bm, Cm, D, delta_bias, dy, du, ddelta, dA, dB, dC, dD, dbias, workspace, workspace_bytes,
+                             batch, dim, L, N, G, delta_softplus, stream, true);
 }
 
 size_t wm_ss2d_core_bwd_workspace_bytes(int B, int D, int H, int W, int N, int R) {
@@ -325,6 +396,35 @@ int wm_ss2d_core_bwd(const float* x, const float* x_proj_weight, const float* dt
                                dy_col_rev, dx, dx_proj_weight, ddt_projs_weight, ddt_projs_bias, dA_logs, dDs, workspace, B, D, H, W, N, R, st);
     return core_bwd_v2<32>(pl, x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, dy_row_fwd, dy_row_rev, dy_col_fwd,
                            dy_col_rev, dx, dx_proj_weight, ddt_projs_weight, ddt_projs_bias, dA_logs, dDs, workspace, B, D, H, W, N, R, st);
+}
+
+size_t wm_linear_wgrad_det_workspace_bytes(int64_t T, int O, int I) {
+    if (T <= 0 || O <= 0 || I <= 0 || O % 16 != 0 || I % 16 != 0 || O * I > 8192) return 0;
+    long long slice;
+    return (size_t)(linear_wgrad_waves((long long)T, slice) / kLwWaves) * O * I * sizeof(float);
+}
+
+int wm_linear_wgrad_det(const float* gy, const float* x, float* dW, void* workspace, size_t workspace_bytes, int64_t T, int O, int I,
+                        void* stream) {
+    if (T < 0 || O <= 0 || I <= 0) return WM_EINVAL;
+    if (!dW) return WM_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    if (T == 0) {
+        const hipError_t e = zero_async(dW, (size_t)O * I * sizeof(float), st);
+        return e == hipSuccess ? WM_OK : (int)e;
+    }
+    if (!gy || !x || !workspace) return WM_ENULL;
+    if (O % 16 != 0 || I % 16 != 0 || O * I > 8192) return WM_EUNSUPPORTED;
+    if (workspace_bytes < wm_linear_wgrad_det_workspace_bytes(T, O, I)) return WM_EWORKSPACE;
+    if (!aligned16(workspace)) return WM_EALIGN;
+    long long slice;
+    const long long nblk = linear_wgrad_waves((long long)T, slice) / kLwWaves;
+#define WM_LW(OT, IT) if (O == 16 * OT && I == 16 * IT) {                                                                    \
+        linear_wgrad_launch<OT, IT, true>(gy, x, (float*)workspace, (long long)T, st);                                       \
+        return det_finish((const float*)workspace, nblk, (long long)O * I, DetOut{dW, nullptr, nullptr, kDetSplit, O * I, 0, 0}, st); }
+    WM_LW(8, 2) WM_LW(2, 4) WM_LW(4, 1) WM_LW(1, 2) WM_LW(2, 1) WM_LW(1, 1) WM_LW(4, 2) WM_LW(2, 2) WM_LW(1, 4)
+#undef WM_LW
+    return WM_EUNSUPPORTED;
 }
 
 int wm_linear_wgrad(const float* gy, const float* x, float* dW, int64_t T, int O, int I, void* stream) {

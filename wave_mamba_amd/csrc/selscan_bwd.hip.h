@@ -50,6 +50,8 @@ struct ScanBwdArgs {
     float *part;                   // [batch*dim][block][NP + kPartPad]
     int batch, dim, L, N, G, dpg, wpg, nchunks, softplus, atomic_bc;
     int cpb, nblocks;              // chunks per block: a block walks cpb consecutive 16-step chunks; blocks per sequence
+    long long bc_slab;             // 0, or (wm_selscan_bwd_det with wpg > 1) the elements of one dB / dC slab: dB, dC then point at wpg
+                                   // slabs in the workspace and the workgroup of channel slice `sub` stores into slab `sub`
 };
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_chunk_kernel(ScanBwdArgs p) {
             const int rr = 16 * i + trow;                              // 0..NP-1: dB n, NP..2NP-1: dC n
             const int n = rr % NP;
             if (n < p.N) {
-                float* base = (rr < NP ? p.dB : p.dC) + bcbase + (long long)n * L + t;
+                float* base = (rr < NP ? p.dB : p.dC) + (long long)(blockIdx.y % p.wpg) * p.bc_slab + bcbase + (long long)n * L + t;
                 const float4 v = *reinterpret_cast<const float4*>(&s_red[rr * kBRow + 4 * tq]);
                 const float vv[4] = {v.x, v.y, v.z, v.w};
                 if (p.atomic_bc) {
@@ -496,6 +498,9 @@ __global__ __launch_bounds__(64) void selscan_bwd_chunk_kernel(ScanBwdArgs p) {
 // dA (dim, N), dD (dim), dbias (dim) = sums of the per-chunk partials over chunks and batch.
 // One block per channel streams its [batch][chunk][NPP] partials (contiguous per batch item); a thread
 // keeps a fixed column j = f mod NPP by striding in multiples of NPP, then an LDS tree over the threads.
+// DET (wm_selscan_bwd_det): `dA` is the workspace and block (d, y) stores its NPP sums as the record fin[(y * dim + d) * NPP ..]
+// (det_finish adds the gridDim.y records of a channel in a fixed order).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void selscan_bwd_finish_kernel(const float* __restrict__ part, float* __restrict__ dA,
                                                                  float* __restrict__ dD, float* __restrict__ dbias,
                                                                  int batch, int dim, int N, int NPP, int nchunks, int NP) {
@@ -517,9 +522,32 @@ __global__ __launch_bounds__(256) void selscan_bwd_finish_kernel(const float* __
     if (t < NPP) {
         float tot = 0.0f;
         for (int q = t; q < stride; q += NPP) tot += s[q];
+        if constexpr (DET) { dA[((long long)blockIdx.y * dim + d) * NPP + t] = tot; return; }
         if (t < N) atomicAdd(dA + (long long)d * N + t, tot);       // outputs are zeroed by the launcher
         else if (t == NP && dD) atomicAdd(dD + d, tot);
         else if (t == NP + 1 && dbias) atomicAdd(dbias + d, tot);
+    }
+}
+
+// out[i] = sum_{w < nslab} slab[w n + i] in ascending w (the dB / dC slabs of wm_selscan_bwd_det).  grid-stride, block (256)
+__global__ __launch_bounds__(256) void det_slab_sum_kernel(const float* __restrict__ slab, float* __restrict__ out, long long n,
+                                                           int nslab, int vec) {
+    const long long stride = (long long)gridDim.x * 256;
+    if (vec) {
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n / 4; i += stride) {
+            float4 a = reinterpret_cast<const float4*>(slab)[i];
+            for (int w = 1; w < nslab; ++w) {
+                const float4 v = reinterpret_cast<const float4*>(slab + (long long)w * n)[i];
+                a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+            }
+            reinterpret_cast<float4*>(out)[i] = a;
+        }
+    } else {
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+            float a = slab[i];
+            for (int w = 1; w < nslab; ++w) a += slab[(long long)w * n + i];
+            out[i] = a;
+        }
     }
 }
 

@@ -112,6 +112,38 @@ def zero_arena_clear():
 
 
 # ------------------------------------------------------------------------------------------------
+# Deterministic training mode: every gradient and the loss value bit-equal run to run.  Off by default.  With it on, the autograd
+# functions whose kernels leave a sum through float atomics - the depth-wise weight gradient, the three LayerNorm backward kernels,
+# the linear weight gradient, plane_sums, the scale_add backward, the L1 mean and the selective-scan backward - call the library's
+# wm_*_det forms (same kernels, same grid, per-workgroup partials in a torch.empty workspace, a fixed-order finish that overwrites
+# torch.empty outputs: no zero arena), and the two channel gathers of the HFE branch go through channel_gather, whose backward is
+# the library's ordered kernel instead of ATen's scatter-add.  The mode is read when an operator is CALLED: a graph captured with
+# it on replays the deterministic kernels whatever the mode is at replay.  WM_DETERMINISTIC=1 in the environment sets the
+# initial value (read at import, like WM_TRAIN_CONV).
+# ------------------------------------------------------------------------------------------------
+_DETERMINISTIC = os.environ.get("WM_DETERMINISTIC", "0")
+if _DETERMINISTIC not in ("0", "1"):
+    raise RuntimeError(f"WM_DETERMINISTIC={_DETERMINISTIC!r}: 0 or 1")
+_DETERMINISTIC = _DETERMINISTIC == "1"
+
+
+def set_deterministic(on):
+    """Switch the deterministic training mode (see above).  Returns the previous setting."""
+    global _DETERMINISTIC
+    prev, _DETERMINISTIC = _DETERMINISTIC, bool(on)
+    return prev
+
+
+def is_deterministic():
+    return _DETERMINISTIC
+
+
+def _det_workspace(nbytes, device):
+    """The uninitialised workspace of a wm_*_det call (None for 0 bytes: an empty problem)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+# ------------------------------------------------------------------------------------------------
 # bf16-storage mode (BASELINE config 2 as worded): the plane tensors an LFSSBlock hands from kernel to kernel - x, z,
 # the conv outputs, the four scan outputs, f, fc - are stored as bfloat16; every kernel computes in fp32 (tiles,
 # projections, scan state, LayerNorm statistics) and the token tensors between blocks stay fp32.  Off by default:
@@ -329,6 +361,12 @@ class _SelectiveScan(torch.autograd.Function):
         dC = torch.empty_like(C)
         dD = torch.empty_like(D) if D is not None else None
         dbias = torch.empty_like(delta_bias) if delta_bias is not None else None
+        if _DETERMINISTIC:
+            ws_bytes = lib.wm_selscan_bwd_det_workspace_bytes(batch, dim, L, N, G)
+            ws = _det_workspace(ws_bytes, u.device)
+            _launch(u.device, "wm_selscan_bwd_det", u, delta, A, B, C, D, delta_bias, dout, du, ddelta, dA, dB, dC, dD, dbias,
+                    ws, ws_bytes, batch, dim, L, N, G, int(ctx.delta_softplus))
+            return du, ddelta, dA, dB, dC, dD, dbias, None, None
         ws_bytes = lib.wm_selscan_bwd_workspace_bytes(batch, dim, L, N, G)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=u.device) if ws_bytes else None
         _launch(u.device, "wm_selscan_bwd", u, delta, A, B, C, D, delta_bias, dout, du, ddelta, dA, dB, dC, dD, dbias,
@@ -738,6 +776,12 @@ class _DWConvTrain(torch.autograd.Function):
         gy = gy.contiguous().float()
         B, C, H, W = x.shape
         gx = dwconv3x3(gy, weight, None, "none", flip=True)
+        if _DETERMINISTIC:
+            dW = torch.empty_like(weight, dtype=torch.float32, memory_format=torch.contiguous_format)
+            db = torch.empty(C, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            nb = _lib.load().wm_dwconv3x3_wgrad_det_workspace_bytes(B, C, H, W)
+            _launch(x.device, "wm_dwconv3x3_wgrad_det", x.contiguous(), gy, dW, db, _det_workspace(nb, x.device), nb, B, C, H, W)
+            return gx, dW, db
         buf = _zeros_small(10 * C, x.device)                                    # dW | db back to back, zeroed
         dW = buf[:9 * C].view(weight.shape)
         db = buf[9 * C:] if ctx.has_bias else None
@@ -766,6 +810,12 @@ class _LayerNorm2dTrain(torch.autograd.Function):
         B, C, H, W = x.shape
         gy = gy.contiguous().float()
         gx = torch.empty_like(x)
+        if _DETERMINISTIC:
+            buf = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+            nb = _lib.load().wm_layernorm2d_bwd_det_workspace_bytes(B, H * W, C)
+            _launch(x.device, "wm_layernorm2d_bwd_det", x, _w(weight), gy, ctx.eps, gx, buf[:C], buf[C:], _det_workspace(nb, x.device),
+                    nb, B, H * W, C)
+            return gx, buf[:C], buf[C:], None
         buf = _zeros_small(2 * C, x.device)                                     # dweight | dbias back to back, zeroed
         dw, db = buf[:C], buf[C:]
         _launch(x.device, "wm_layernorm2d_bwd", x, _w(weight), gy, ctx.eps, gx, dw, db, B, H * W, C)
@@ -796,6 +846,12 @@ class _LayerNormTok(torch.autograd.Function):
         C = x.shape[-1]
         gy = gy.contiguous().float()
         gx = torch.empty_like(x)
+        if _DETERMINISTIC:
+            buf = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+            T = x.numel() // C
+            nb = _lib.load().wm_layernorm_tok_bwd_det_workspace_bytes(T, C)
+            _launch(x.device, "wm_layernorm_tok_bwd_det", x, w, gy, ctx.eps, gx, buf[:C], buf[C:], _det_workspace(nb, x.device), nb, T, C)
+            return gx, buf[:C], buf[C:], None
         buf = _zeros_small(2 * C, x.device)
         dw, db = buf[:C], buf[C:]
         _launch(x.device, "wm_layernorm_tok_bwd", x, w, gy, ctx.eps, gx, dw, db, x.numel() // C, C)
@@ -932,6 +988,11 @@ class _ScaleAdd(torch.autograd.Function):
         g = g.contiguous().float()
         B, C = x.shape[:2]
         L = x[0, 0].numel()
+        if _DETERMINISTIC:
+            gx, gs = torch.empty_like(x), torch.empty(C, dtype=torch.float32, device=x.device)
+            nb = _lib.load().wm_scale_add_bwd_det_workspace_bytes(B, C, L)
+            _launch(x.device, "wm_scale_add_bwd_det", g, x, sc, gx, gs, _det_workspace(nb, x.device), nb, B, C, L)
+            return gx, gs.view(ctx.scale_shape), g
         gx, gs = torch.empty_like(x), _zeros_small(C, x.device)
         _launch(x.device, "wm_scale_add_bwd", g, x, sc, gx, gs, B, C, L)
         return gx, gs.view(ctx.scale_shape), g
@@ -1563,6 +1624,11 @@ class _LinearNoBias(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             O, I = weight.shape
             g2, x2 = gy.reshape(-1, O).contiguous().float(), x.reshape(-1, I).contiguous().float()
+            if _DETERMINISTIC:
+                gw = torch.empty(O, I, dtype=torch.float32, device=x.device)
+                nb = _lib.load().wm_linear_wgrad_det_workspace_bytes(g2.shape[0], O, I)
+                _launch(x.device, "wm_linear_wgrad_det", g2, x2, gw, _det_workspace(nb, x.device), nb, g2.shape[0], O, I)
+                return gx, gw
             gw = _zeros_small(O * I, x.device).view(O, I)
             _launch(x.device, "wm_linear_wgrad", g2, x2, gw, g2.shape[0], O, I)
         return gx, gw
@@ -1579,11 +1645,66 @@ def linear_nobias(x, weight):
     return _LinearNoBias.apply(x, weight)
 
 
+class _ChannelGather(torch.autograd.Function):
+    """y[b, j] = x[b, index[b, j]] over the channel axis of (B, C, ...) fp32 maps, index (B, M): wm_channel_gather_fwd, and for the
+    gradient wm_channel_gather_bwd - every channel's sources added in ascending j, no atomics (ATen's scatter-add has no order)."""
+
+    @staticmethod
+    def forward(ctx, x, index):
+        B, C = x.shape[:2]
+        M = index.shape[1]
+        HW = x[0, 0].numel() if B and C else 0
+        idx = index.to(torch.int32).contiguous()
+        y = torch.empty((B, M) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        _launch(x.device, "wm_channel_gather_fwd", x, idx, y, B, C, M, HW)
+        ctx.save_for_backward(idx)
+        ctx.x_shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        idx, = ctx.saved_tensors
+        B, C = ctx.x_shape[:2]
+        M = idx.shape[1]
+        gy = gy.contiguous().float()
+        gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gy.device)
+        _launch(gy.device, "wm_channel_gather_bwd", gy, idx, gx, B, C, M, gx[0, 0].numel() if B and C else 0)
+        return gx, None
+
+
+CHANNEL_GATHER_MAX_M = 1024                # csrc/det.hip.h: kGatherMaxM
+
+
+def channel_gather_supported(x, index):
+    """Operands _ChannelGather covers: a CUDA fp32 (B, C, ...) map with C >= 1, an integer (B, M) index, B, C, M within the grid."""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and index.dim() == 2 and index.shape[0] == x.shape[0]
+            and not index.dtype.is_floating_point and 1 <= x.shape[1] <= 65535 and x.shape[0] <= 65535
+            and index.shape[1] <= CHANNEL_GATHER_MAX_M)
+
+
+def channel_gather(x, index):
+    """torch.gather(x, 1, index[:, :, None, ...].expand(...)) for x (B, C, *plane) and index (B, M) -> (B, M, *plane): the gathers of
+    the HFE branch (Matching's matched maps, PAConv's second input).  CPU tensors take torch.gather (ordered there already); CUDA
+    tensors the HIP kernels, whose gradient is bit-reproducible."""
+    if not x.is_cuda:
+        full = index.long().reshape(index.shape + (1,) * (x.dim() - 2)).expand(-1, -1, *x.shape[2:])
+        return torch.gather(x, 1, full)
+    _require_cuda("channel_gather", x, index)
+    if not channel_gather_supported(x, index):
+        raise NotImplementedError("channel_gather: a float32 (B, C, ...) map and an integer (B, M) index, M <= 1024")
+    return _ChannelGather.apply(x.contiguous(), index)
+
+
 def plane_sums(x):
     """x (B, C, H, W) fp32 -> (C,) sums over batch and plane (bias gradient of a convolution)."""
     _require_cuda("plane_sums", x)
     B, C, H, W = x.shape
     x = x.contiguous().float()
+    if _DETERMINISTIC:
+        out = torch.empty(C, dtype=torch.float32, device=x.device)
+        nb = _lib.load().wm_plane_sums_det_workspace_bytes(B, C, H, W)
+        _launch(x.device, "wm_plane_sums_det", x, out, _det_workspace(nb, x.device), nb, B, C, H, W)
+        return out
     out = _zeros_small(C, x.device)
     _launch(x.device, "wm_plane_sums", x, out, B, C, H, W)
     return out
@@ -1598,6 +1719,11 @@ class _L1Mean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         ctx.save_for_backward(a, b)
+        if _DETERMINISTIC:
+            out = torch.empty(1, dtype=torch.float32, device=a.device)
+            nb = _lib.load().wm_l1_mean_fwd_det_workspace_bytes(a.numel())
+            _launch(a.device, "wm_l1_mean_fwd_det", a, b, out, _det_workspace(nb, a.device), nb, a.numel())
+            return out.reshape(())
         out = _zeros_small(1, a.device)
         _launch(a.device, "wm_l1_mean_fwd", a, b, out, a.numel())
         return out.reshape(())
@@ -1764,6 +1890,18 @@ def _conv_weight_grad(gy, x, weight, with_bias=False):
     never dies on a shape, as conv_wgrad.hip.h promises.  with_bias: -> (dW, db), the bias gradient from the same kernel (or
     plane_sums next to ATen's weight gradient)."""
     ks = weight.shape[2]
+    if _DETERMINISTIC and _TRAIN_CONV_WGRAD_HIP and x.is_cuda and x.shape[3] % 32 != 0:
+        # Deterministic mode: MIOpen's weight-gradient kernels are not ordered (measured: the 16-wide maps of a 64 x 64 crop, 39
+        # weight tensors of the shipped network differing run to run), so maps the HIP kernel refuses for their width go to it
+        # with gy and x zero-padded on the right to a multiple of 32 columns - the padded columns of gy contribute nothing and
+        # those of x are the convolution's own zero padding: the same sums, added in the kernel's fixed order.
+        pad = -x.shape[3] % 32
+        xp, gp = F.pad(x.float(), (0, pad)), F.pad(gy.float(), (0, pad))
+        if conv2d_wgrad_supported(xp, weight):
+            try:
+                return conv2d_wgrad(gp, xp, ks, _refusal=_WgradRefused, with_bias=with_bias)
+            except _WgradRefused:
+                pass
     if _TRAIN_CONV_WGRAD_HIP and conv2d_wgrad_supported(x, weight):
         try:
             return conv2d_wgrad(gy, x, ks, _refusal=_WgradRefused, with_bias=with_bias)
@@ -1866,7 +2004,7 @@ def conv2d_supported(x, weight, x2=None):
 PROF_KERNELS = ("haar_analysis", "haar_synthesis", "selscan_chunk_reduce", "selscan_carry",
                 "selscan_chunk_scan", "lfss_in", "ss2d_proj", "dwconv3x3",
                 "ss2d_core_scan", "lfss_mid", "ss2d_core_reduce", "lfss_out", "selscan_bwd",
-                "conv3x3", "conv1x1", "skff", "layernorm2d", "dwconv3x3_other", "patchify_conv", "unused_19")
+                "conv3x3", "conv1x1", "skff", "layernorm2d", "dwconv3x3_other", "patchify_conv", "det_finish")
 
 
 def prof_enable(on=True):
