@@ -60,6 +60,47 @@ def test_argument_validation_returns_before_launch():
     assert lib.wm_selscan_fwd(*([None] * 10), None, 0, 0, 8, 16, 4, 2, 1, None) == 0
 
 
+def test_deterministic_forms_and_gathers_validate_before_launch():
+    """The wm_*_det entry points and the channel gathers refuse a negative size, a NULL output and an unsupported width by host
+    arithmetic alone, and their workspace queries answer 0 for an empty or unsupported shape (the refusals that need real device
+    buffers - a short or NULL workspace, the gather's M limit, an odd pointer: tests/test_deterministic_reference.py, on the GPU)."""
+    lib = _lib.load()
+    N, EINVAL, ENULL, EUNSUP = None, _lib.WM_EINVAL, _lib.WM_ENULL, _lib.WM_EUNSUPPORTED
+    assert lib.wm_dwconv3x3_wgrad_det(N, N, N, N, N, 0, -1, 4, 6, 8, N) == EINVAL
+    assert lib.wm_dwconv3x3_wgrad_det(N, N, N, N, N, 0, 2, 4, 6, 8, N) == ENULL
+    assert lib.wm_dwconv3x3_wgrad_det(N, N, N, N, N, 0, 2, 0, 6, 8, N) == 0                   # no channel: nothing to write
+    assert lib.wm_layernorm2d_bwd_det(N, N, N, 1e-6, N, N, N, N, 0, -1, 35, 16, N) == EINVAL
+    assert lib.wm_layernorm2d_bwd_det(N, N, N, 1e-6, N, N, N, N, 0, 2, 35, 12, N) == EUNSUP
+    assert lib.wm_layernorm2d_bwd_det(N, N, N, 1e-6, N, N, N, N, 0, 2, 35, 16, N) == ENULL
+    assert lib.wm_layernorm_tok_bwd_det(N, N, N, 1e-5, N, N, N, N, 0, -1, 16, N) == EINVAL
+    assert lib.wm_layernorm_tok_bwd_det(N, N, N, 1e-5, N, N, N, N, 0, 37, 12, N) == EUNSUP
+    assert lib.wm_layernorm_tok_bwd_det(N, N, N, 1e-5, N, N, N, N, 0, 37, 16, N) == ENULL
+    assert lib.wm_linear_wgrad_det(N, N, N, N, 0, -1, 16, 16, N) == EINVAL
+    assert lib.wm_linear_wgrad_det(N, N, N, N, 0, 100, 16, 16, N) == ENULL
+    assert lib.wm_plane_sums_det(N, N, N, 0, -1, 3, 5, 7, N) == EINVAL
+    assert lib.wm_plane_sums_det(N, N, N, 0, 2, 3, 5, 7, N) == ENULL
+    assert lib.wm_plane_sums_det(N, N, N, 0, 2, 0, 5, 7, N) == 0
+    assert lib.wm_scale_add_bwd_det(N, N, N, N, N, N, 0, 2, 4, -1, N) == EINVAL
+    assert lib.wm_scale_add_bwd_det(N, N, N, N, N, N, 0, 2, 4, 35, N) == ENULL
+    assert lib.wm_l1_mean_fwd_det(N, N, N, N, 0, -1, N) == EINVAL
+    assert lib.wm_l1_mean_fwd_det(N, N, N, N, 0, 1000, N) == ENULL
+    scan = lambda batch, dim, L, n, G: lib.wm_selscan_bwd_det(*([N] * 15), N, 0, batch, dim, L, n, G, 1, N)
+    assert scan(-1, 8, 20, 4, 2) == EINVAL and scan(1, 8, 20, 4, 3) == EINVAL                 # a negative size; dim % G
+    assert scan(1, 8, 20, 40, 2) == EUNSUP and scan(1, 8, 20, 4, 2) == ENULL                  # N > 32; NULL tensors
+    assert scan(0, 8, 20, 4, 2) == 0                                                          # empty, and nothing to zero (NULL outputs)
+    assert lib.wm_dwconv3x3_wgrad_det_workspace_bytes(0, 4, 6, 8) == 0 and lib.wm_dwconv3x3_wgrad_det_workspace_bytes(2, 4, 6, 8) > 0
+    assert lib.wm_layernorm2d_bwd_det_workspace_bytes(2, 35, 12) == 0 and lib.wm_layernorm_tok_bwd_det_workspace_bytes(37, 12) == 0
+    assert lib.wm_linear_wgrad_det_workspace_bytes(100, 15, 16) == 0 and lib.wm_linear_wgrad_det_workspace_bytes(100, 16, 16) == 16 * 16 * 4
+    assert lib.wm_plane_sums_det_workspace_bytes(2, 3, 5, 0) == 0 and lib.wm_scale_add_bwd_det_workspace_bytes(0, 4, 35) == 0
+    assert lib.wm_l1_mean_fwd_det_workspace_bytes(0) == 0 and lib.wm_l1_mean_fwd_det_workspace_bytes(5) == 4096
+    assert lib.wm_selscan_bwd_det_workspace_bytes(1, 8, 20, 40, 2) == 0 and lib.wm_selscan_bwd_det_workspace_bytes(1, 8, 20, 4, 2) > 0
+    # the channel gathers: a negative size, C = 0 with something to gather, NULL tensors; empty problems are a no-op
+    assert lib.wm_channel_gather_fwd(N, N, N, 1, 2, -1, 4, N) == EINVAL and lib.wm_channel_gather_bwd(N, N, N, 1, 2, 5, -4, N) == EINVAL
+    assert lib.wm_channel_gather_fwd(N, N, N, 1, 0, 5, 4, N) == EINVAL
+    assert lib.wm_channel_gather_fwd(N, N, N, 1, 2, 5, 4, N) == ENULL and lib.wm_channel_gather_bwd(N, N, N, 1, 2, 5, 4, N) == ENULL
+    assert lib.wm_channel_gather_fwd(N, N, N, 0, 2, 5, 4, N) == 0 and lib.wm_channel_gather_bwd(N, N, N, 1, 2, 5, 0, N) == 0
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/libwavemamba_hip.so")

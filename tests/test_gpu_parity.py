@@ -307,13 +307,16 @@ def test_scan_backward_vs_oracle(batch, dim, L, N, G):
             assert_close(got, ref, TOL, f"{name}")
 
 
-def scan_grads_f64(u, delta, A, Bm, Cm, D, bias, dy):
-    """The selective-scan definition in float64 with autograd: truth for the reduced gradients."""
-    leaves = [t.double().requires_grad_(True) for t in (u, delta, A, Bm, Cm, D, bias)]
+def scan_grads_f64(u, delta, A, Bm, Cm, D, bias, dy, delta_softplus=True):
+    """The selective-scan definition in float64 with autograd: truth for the reduced gradients.  D and bias
+    may be None (no skip term / no step bias): their gradients are then left out of the result."""
+    leaves = [None if t is None else t.double().requires_grad_(True) for t in (u, delta, A, Bm, Cm, D, bias)]
     u_, dl, A_, B_, C_, D_, b_ = leaves
     batch, dim, L = u_.shape
     N, G = A_.shape[1], B_.shape[1]
-    dt = F.softplus(dl + b_.view(1, dim, 1))
+    dt = dl if b_ is None else dl + b_.view(1, dim, 1)
+    if delta_softplus:
+        dt = F.softplus(dt)
     Bf = B_.repeat_interleave(dim // G, dim=1)          # (b, dim, N, L)
     Cf = C_.repeat_interleave(dim // G, dim=1)
     h = torch.zeros(batch, dim, N, dtype=torch.float64)
@@ -322,14 +325,23 @@ def scan_grads_f64(u, delta, A, Bm, Cm, D, bias, dy):
     for dt_t, du_t, B_t, C_t in zip(dt.unbind(2), (dt * u_).unbind(2), Bf.unbind(3), Cf.unbind(3)):
         h = torch.exp(dt_t[..., None] * A_.view(1, dim, N)) * h + du_t[..., None] * B_t
         ys.append((h * C_t).sum(-1))
-    y = torch.stack(ys, 2) + u_ * D_.view(1, dim, 1)
-    g = torch.autograd.grad(y, leaves, dy.double())
-    return dict(zip(GRAD_NAMES, g))
+    y = torch.stack(ys, 2)
+    if D_ is not None:
+        y = y + u_ * D_.view(1, dim, 1)
+    names = [n for n, t in zip(GRAD_NAMES, leaves) if t is not None]
+    g = torch.autograd.grad(y, [t for t in leaves if t is not None], dy.double())
+    return dict(zip(names, g))
 
 
 def test_training_step_on_gpu_matches_reference(golden):
     """One optimize_parameters() of the reference trainer on the HIP path (module glue + HIP scan fwd/bwd +
     HIP DWT/IWT fwd/bwd) against the reference's gradient fingerprints (tests/golden/model_shipped_meta.json)."""
+    check_shipped64_fingerprints()
+
+
+def check_shipped64_fingerprints():
+    """The body of test_training_step_on_gpu_matches_reference (tests/test_deterministic_reference.py runs it with the deterministic
+    training mode on) -> (worst fingerprint error, the reference's fp32 error on that tensor, its name)."""
     import json, os
     from conftest import GOLDEN
     meta = json.load(open(os.path.join(GOLDEN, "model_shipped_meta.json")))
@@ -343,17 +355,20 @@ def test_training_step_on_gpu_matches_reference(golden):
     # (sum, abs-sum) fingerprints only at 1.5 M parameters (the full tensors are checked on the wf = 8 model below):
     # the build's and the reference's fp32 fingerprints against the float64 ones
     fp = lambda a, b: max(abs(a[0] - b[0]), abs(a[1] - b[1])) / max(b[1], 1e-30)
-    bad = []
+    bad, worst = [], (0.0, 0.0, None)
     for k, p in net.named_parameters():
         assert p.grad is not None and torch.isfinite(p.grad).all(), k
         g = p.grad.double()
         truth = meta["grad_fingerprint_f64"][k]
         e_got = fp((float(g.sum()), float(g.abs().sum())), truth)
         e_ref = max(fp(meta["grad_fingerprint"][k], truth), meta["grad_ref32_vs_f64"][k])
+        worst = max(worst, (e_got, e_ref, k))
         if e_got > truth_bar(e_ref):
             bad.append((e_got, e_ref, k))
+    print("shipped config 64 x 64: worst gradient fingerprint error vs float64 %.3e (reference fp32 %.3e) %s" % worst)
     assert not bad, "gradient fingerprints off the float64 truth (build, reference fp32, name): " + \
         "; ".join("%.3e %.3e %s" % b for b in sorted(bad, reverse=True)[:5])
+    return worst
 
 
 def test_training_step_per_parameter_gradients_on_gpu():
@@ -361,6 +376,12 @@ def test_training_step_per_parameter_gradients_on_gpu():
     DWT / IWT, depth-wise conv, LayerNorms, convolutions' input gradients in HIP, the rest PyTorch autograd: every
     parameter's gradient TENSOR against the float64 evaluation of the reference's code, judged against what the
     reference's own fp32 autograd (tests/golden/train_grads_wf8.npz) achieves on the same tensor."""
+    check_wf8_step_gradients()
+
+
+def check_wf8_step_gradients():
+    """The body of test_training_step_per_parameter_gradients_on_gpu (tests/test_deterministic_reference.py runs it with the
+    deterministic training mode on) -> (worst gradient error, the reference's fp32 error on that tensor, its name)."""
     import numpy as np, os
     from conftest import GOLDEN
     from test_arch_cpu import grad_golden_case
@@ -384,6 +405,7 @@ def test_training_step_per_parameter_gradients_on_gpu():
     print("worst per-parameter gradient error vs float64 truth: %.3e (reference fp32 %.3e) %s" % worst)
     assert not bad, "gradients off the float64 truth (build, reference fp32, name): " + \
         "; ".join("%.3e %.3e %s" % b for b in sorted(bad, reverse=True)[:8])
+    return worst
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2765,8 +2787,13 @@ def test_training_step_shipped_config_256_vs_reference(golden):
     convolution - against the REFERENCE's own autograd (tests/golden/train_grads_shipped256.npz, make_golden_grads_256.py):
     losses, prediction, and EVERY parameter gradient (whole tensor up to 1,024 elements, else 1,024 strided elements + whole-
     tensor sums) judged against the float64 evaluation of the reference's code like every gradient test of this file."""
+    check_shipped256_step(golden("train_grads_shipped256"))
+
+
+def check_shipped256_step(g):
+    """The body of test_training_step_shipped_config_256_vs_reference on the golden `g` (tests/test_deterministic_reference.py
+    runs it with the deterministic training mode on) -> (worst gradient error, the reference's fp32 error on that tensor, its name)."""
     import bench
-    g = golden("train_grads_shipped256")
     torch.manual_seed(0)
     net = wm.WaveMamba(**bench.SHIPPED).train().to(DEV)
     lq = torch.rand(2, 3, 256, 256, generator=gen(1234)).to(DEV)
@@ -2803,6 +2830,7 @@ def test_training_step_shipped_config_256_vs_reference(golden):
     print("shipped config 256 x 256, %d tensors: worst gradient error vs float64 truth %.3e (reference fp32 %.3e) %s" % ((n,) + worst))
     assert not bad, "gradients off the float64 truth (build, reference fp32, name): " + \
         "; ".join("%.3e %.3e %s" % b for b in sorted(bad, reverse=True)[:8])
+    return worst
 
 
 @pytest.mark.parametrize("ks,B,Cin,Cout,H,W", [

@@ -295,7 +295,18 @@ static int selscan_bwd_entry(const float* u, const float* delta, const float* A,
                              float* dA, float* dB, float* dC, float* dD, float* dbias, void* workspace,
                              size_t workspace_bytes, int batch, int dim, int L, int N, int G, int delta_softplus,
                              void* stream, bool det) {
-    if (batch == 0 || dim == 0 || L == 0) return (batch < 0 || dim < 0 || L < 0) ? WM_EINVAL : WM_OK;
+    if (batch == 0 || dim == 0 || L == 0) {
+        if (batch < 0 || dim < 0 || L < 0) return WM_EINVAL;
+        // the deterministic form's caller hands it uninitialised outputs: an empty problem's parameter gradients are zero, not
+        // whatever the memory held (the other gradients have no element then)
+        if (det && dim > 0 && N > 0 && N <= 32) {
+            hipStream_t st = (hipStream_t)stream;
+            hipError_t e = dA ? zero_out(dA, (size_t)dim * N * sizeof(float), st) : hipSuccess;
+            if (e == hipSuccess) e = zero_pair(dD, dD ? (size_t)dim : 0, dbias, dbias ? (size_t)dim : 0, st);
+            if (e != hipSuccess) return (int)e;
+        }
+        return WM_OK;
+    }
     BwdPlan pl;
     int rc = bwd_plan(pl, batch, dim, L, N, G);
     if (rc) return rc;

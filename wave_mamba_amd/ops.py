@@ -120,6 +120,11 @@ def zero_arena_clear():
 # the library's ordered kernel instead of ATen's scatter-add.  The mode is read when an operator is CALLED: a graph captured with
 # it on replays the deterministic kernels whatever the mode is at replay.  WM_DETERMINISTIC=1 in the environment sets the
 # initial value (read at import, like WM_TRAIN_CONV).
+# The dense convolutions' weight gradient (_conv_weight_grad) goes to wm_conv2d_wgrad at every map width in the mode (zero-padded on
+# the right to a multiple of 32 columns).  What stays on ATen's unordered weight gradient even then: output channels whose count,
+# rounded up to 16s, is not 1, 2, 4 or 6 - 33 .. 48, 65 .. 80 and more than 96 output channels, 3x3 and 1x1 alike - for which the
+# kernel has no form at any width (conv2d_wgrad_supported, whose `ks == 3 and 64 < Cout <= 80` clause that rule contains).  The
+# shipped configuration (wf = 32) has no such convolution; a network of wf = 48 has them throughout.
 # ------------------------------------------------------------------------------------------------
 _DETERMINISTIC = os.environ.get("WM_DETERMINISTIC", "0")
 if _DETERMINISTIC not in ("0", "1"):
@@ -975,7 +980,7 @@ class _ScaleAdd(torch.autograd.Function):
     def forward(ctx, x, scale, o):
         x, o, sc = x.contiguous().float(), o.contiguous().float(), _w(scale)
         B, C = x.shape[:2]
-        L = x[0, 0].numel()
+        L = x.shape[2:].numel()                                                 # (not x[0, 0].numel(): an empty batch has no x[0])
         out = torch.empty_like(x)
         _launch(x.device, "wm_scale_add_fwd", x, sc, o, out, B, C, L)
         ctx.save_for_backward(x, sc)
@@ -987,7 +992,7 @@ class _ScaleAdd(torch.autograd.Function):
         x, sc = ctx.saved_tensors
         g = g.contiguous().float()
         B, C = x.shape[:2]
-        L = x[0, 0].numel()
+        L = x.shape[2:].numel()
         if _DETERMINISTIC:
             gx, gs = torch.empty_like(x), torch.empty(C, dtype=torch.float32, device=x.device)
             nb = _lib.load().wm_scale_add_bwd_det_workspace_bytes(B, C, L)
