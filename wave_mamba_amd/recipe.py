@@ -1,0 +1,436 @@
+"""Training from the reference's recipe (options/train_wavemamba_uhdll.yml): options, sampler, the iteration loop of
+basicsr/train.py:197-264 with its checkpoint cadence, validation with best-model bookkeeping (femasr_model.py:187-303,
+base_model.py:50-83) and exact resume - around the pieces this package already has (data.PairedPatchBatcher, trainer.train_step /
+GraphedTrainStep, schedulers, ops.psnr_ssim_y).
+
+    opt, derived = load_options("train_wavemamba_uhdll.yml", num_train=len(store))
+    Trainer(opt, train_store, val_store, graphed=True, out_dir="experiments/run").run()
+
+    python -m wave_mamba_amd.recipe -opt FILE --train-pairs DIR [--val-pairs DIR] [--eager] [--out-dir DIR]
+
+Single process: `rank` and `world` reach the sampler and the seeds only (the data-parallel GraphedDDPTrainStep is not wired in).
+Out of scope: decoding image files (pairs are uint8 arrays), TensorBoard / wandb, LPIPS (skipped with a warning), saving
+validation images.
+
+Validation metrics.  The reference scores with `pyiqa` (femasr_model.py:39), a package that is not in its tree.  Here `psnr` and
+`ssim` are this project's metrics.py - the reference's own comput_psnr_ssim.py, Y channel, on the uint8 image that tensor2img
+produces - computed on the device by ops.psnr_ssim_y.
+
+Graphed mode and "one loop iteration = one recipe iteration".  GraphedTrainStep's constructor runs three warm-up steps on a side
+stream before it captures; they are real optimizer steps.  The loop saves weights, moments and step counters before the
+constructor and restores them IN PLACE after it (the graph reads those very tensors), so the warm-up leaves no trace and every
+iteration - the first one and the first one after a resume included - is one replay.
+"""
+import json
+import logging
+import math
+import os
+
+import torch
+
+from . import schedulers, trainer
+from .data import DeviceImageStore, PairedPatchBatcher
+from .registry import build_network
+
+LOG = logging.getLogger("wave_mamba_amd")
+_OPTIM_KEYS = ("type", "lr", "weight_decay", "betas")
+
+
+# ---- options ---------------------------------------------------------------------------------------------------------------------
+def _get(opt, dotted, default=None):
+    for key in dotted.split("."):
+        if not isinstance(opt, dict) or opt.get(key) is None:
+            return default
+        opt = opt[key]
+    return opt
+
+
+def usable_metrics(opt, warn=False):
+    """{name: {"type", "crop_border", "better"}} of val.metrics that this package computes.  `lpips` is skipped (warn=True: with a
+    warning - Trainer gives it once, when it sets up its validation); anything else but psnr / ssim on the Y channel is refused with a ValueError that names the key."""
+    out = {}
+    for name, m in (_get(opt, "val.metrics", {}) or {}).items():
+        kind = m.get("type")
+        if kind == "lpips":
+            if warn:
+                LOG.warning("val.metrics.%s: type lpips is not computed here; the metric is skipped", name)
+            continue
+        if kind not in ("psnr", "ssim"):
+            raise ValueError(f"val.metrics.{name}.type: {kind!r} is not implemented (psnr, ssim; lpips is skipped)")
+        if not m.get("test_y_channel", False):           # the reference's metric package defaults to false as well
+            raise ValueError(f"val.metrics.{name}.test_y_channel: false is not implemented - only the Y-channel {kind} "
+                             "(comput_psnr_ssim.py) runs on the device; the 3-channel SSIM does not exist here")
+        out[name] = {"type": kind, "crop_border": int(m.get("crop_border", 0)), "better": m.get("better", "higher")}
+    return out
+
+
+def check_options(opt):
+    """Refuse up front what the loop cannot do; every ValueError names the offending key."""
+    if opt.get("scale", 1) != 1:
+        raise ValueError(f"scale: {opt.get('scale')!r} is not implemented - the recipe trains at scale 1")
+    optim = _get(opt, "train.optim_g")
+    if optim is None:
+        raise ValueError("train.optim_g: missing")
+    if optim.get("type") != "AdamW":
+        raise ValueError(f"train.optim_g.type: {optim.get('type')!r} is not implemented (AdamW)")
+    for key in optim:
+        if key not in _OPTIM_KEYS:
+            raise ValueError(f"train.optim_g.{key}: not an argument of trainer.make_optimizer ({', '.join(_OPTIM_KEYS)})")
+    for key in ("network_g", "train.scheduler", "train.total_iter", "datasets.train.gt_size", "datasets.train.batch_size_per_gpu",
+                "logger.print_freq", "logger.save_checkpoint_freq"):
+        if _get(opt, key) is None:
+            raise ValueError(f"{key}: missing")
+    metrics = usable_metrics(opt)
+    key_metric = _get(opt, "val.key_metric")
+    if opt.get("val") is not None and key_metric is not None and key_metric not in metrics:
+        raise ValueError(f"val.key_metric: {key_metric!r} is not one of the metrics computed here ({', '.join(metrics) or 'none'})")
+
+
+def derive_iters(opt, num_train, world_size=1):
+    """train.py:66-71 -> {"num_iter_per_epoch", "total_iters", "total_epochs"}."""
+    ds = opt["datasets"]["train"]
+    ratio = ds.get("dataset_enlarge_ratio", 1)
+    per_epoch = math.ceil(num_train * ratio / (ds["batch_size_per_gpu"] * world_size))
+    total_iters = int(opt["train"]["total_iter"])
+    return {"num_iter_per_epoch": per_epoch, "total_iters": total_iters, "total_epochs": math.ceil(total_iters / per_epoch)}
+
+
+def load_options(path_or_text, num_train=None, world_size=1):
+    """The recipe as a dict (yaml.safe_load: the `!!float` tags of the shipped file are standard YAML), checked by check_options.
+    `path_or_text`: a file name, or the YAML text itself (anything with a line break).  -> (opt, derived): derived is
+    derive_iters(opt, num_train, world_size), or None while the number of training pairs is not known."""
+    import yaml
+    text = path_or_text
+    if "\n" not in path_or_text:
+        with open(path_or_text, encoding="utf-8") as f:
+            text = f.read()
+    opt = yaml.safe_load(text)
+    if not isinstance(opt, dict):
+        raise ValueError("load_options: the YAML document is not a mapping")
+    check_options(opt)
+    return opt, (None if num_train is None else derive_iters(opt, num_train, world_size))
+
+
+# ---- sampler ---------------------------------------------------------------------------------------------------------------------
+class EnlargedSampler:
+    """basicsr/data/data_sampler.py: ceil(n * ratio / num_replicas) indices per replica and epoch - torch.randperm of the enlarged
+    range from a generator seeded with the epoch, % n, then every num_replicas-th index starting at `rank`.  `n` is the number of
+    pairs (the reference takes the dataset and reads its length)."""
+
+    def __init__(self, n, num_replicas=1, rank=0, ratio=1):
+        self.n, self.num_replicas, self.rank, self.epoch = int(n), int(num_replicas), int(rank), 0
+        self.num_samples = math.ceil(self.n * ratio / self.num_replicas)
+        self.total_size = self.num_samples * self.num_replicas
+
+    def __iter__(self):
+        g = torch.Generator()
+        g.manual_seed(self.epoch)
+        indices = [v % self.n for v in torch.randperm(self.total_size, generator=g).tolist()]
+        return iter(indices[self.rank:self.total_size:self.num_replicas])
+
+    def __len__(self):
+        return self.num_samples
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+
+    def batches(self, batch_size):
+        """The epoch's batches: `batch_size` consecutive indices each, the last short one dropped (data/__init__.py:91)."""
+        idx = list(self)
+        return [idx[i:i + batch_size] for i in range(0, len(idx) - batch_size + 1, batch_size)]
+
+
+# ---- best-model bookkeeping --------------------------------------------------------------------------------------------------------
+class BestMetrics:
+    """base_model.py:50-83 for one validation set.  A metric is `higher` unless it carries `better: lower`; a tie is an update.
+    update(results, current_iter, key_metric) -> True when the best model is to be saved: with a key metric, when THAT metric
+    was updated (every metric's record then takes this validation's value, femasr_model.py:277-288); without one, when any was."""
+
+    def __init__(self, metrics):
+        self.records = {name: {"better": m.get("better", "higher"),
+                               "val": float("-inf") if m.get("better", "higher") == "higher" else float("inf"), "iter": -1}
+                        for name, m in metrics.items()}
+
+    def _update_best(self, name, val, current_iter):
+        rec = self.records[name]
+        if (val >= rec["val"]) if rec["better"] == "higher" else (val <= rec["val"]):
+            rec["val"], rec["iter"] = val, current_iter
+            return True
+        return False
+
+    def update(self, results, current_iter, key_metric=None):
+        if key_metric is not None:
+            if not self._update_best(key_metric, results[key_metric], current_iter):
+                return False
+            for name, val in results.items():
+                self.records[name]["val"], self.records[name]["iter"] = val, current_iter
+            return True
+        return any([self._update_best(name, val, current_iter) for name, val in results.items()])
+
+
+# ---- the loop ----------------------------------------------------------------------------------------------------------------------
+def _freq(value):
+    return None if value is None else int(float(value))
+
+
+class Trainer:
+    """The reference's train_pipeline for one process.
+
+    opt          the recipe: a dict, a file name or YAML text (load_options)
+    train_store  data.DeviceImageStore of the training pairs, on the device to train on (a 'cpu' store trains on the CPU)
+    val_store    a store of whole validation pairs (H, W multiples of 8 as the arch's test() needs them, or padded up by reflection)
+    graphed      True on a GPU: GraphedTrainStep through graphed_step_with_batcher, optimizer from make_optimizer(capturable=True);
+                 False (and always on the CPU): train_step(..., as_float=False)
+    step_fn      step_fn(lq, gt) -> {name: 0-dim tensor} in place of the step (tests)
+    net          a ready network in place of build_network(opt["network_g"])
+
+    run(max_iters=None, on_iter=None) trains to the recipe's end; `max_iters` pauses after that many iterations (no end-of-training
+    save / validation then; run() again continues).  on_iter(current_iter, epoch, lrs, rows, losses) is called after every step:
+    host values, and the step's 0-dim device losses (valid until the next step).  Files: out_dir/models/net_g_{iter}.pth,
+    net_g_latest.pth, net_g_best_{iter}.pth (net_g_best_.pth without a key metric), out_dir/training_states/{iter}.state,
+    out_dir/train.log (one JSON object per line; the same lines go to the `wave_mamba_amd` logger)."""
+
+    def __init__(self, opt, train_store, val_store=None, device=None, graphed=True, out_dir=".", rank=0, world=1, step_fn=None,
+                 net=None):
+        if not isinstance(opt, dict):
+            opt, _ = load_options(opt)
+        else:
+            check_options(opt)
+        self.opt, self.train_store, self.val_store, self.rank, self.world = opt, train_store, val_store, int(rank), int(world)
+        self.device = torch.device(device) if device is not None else train_store.device
+        if self.device != train_store.device or (val_store is not None and val_store.device != self.device):
+            raise ValueError(f"Trainer: the stores must live on the training device {self.device}")
+        self.graphed = bool(graphed) and self.device.type == "cuda" and step_fn is None
+        self.step_fn = step_fn
+        self.out_dir = str(out_dir)
+        ds, tr = opt["datasets"]["train"], opt["train"]
+        seed = opt.get("manual_seed")
+        self.batch_size = int(ds["batch_size_per_gpu"])
+        self.fft_weight = float(_get(opt, "train.fft_opt.loss_weight", 0.1))
+        ssim = _get(opt, "train.pixel_ssim_opt.loss_weight")
+        self.ssim_weight = None if ssim is None else float(ssim)
+        self.warmup_iter = int(tr.get("warmup_iter", -1))
+        self.print_freq, self.save_freq = _freq(opt["logger"]["print_freq"]), _freq(opt["logger"]["save_checkpoint_freq"])
+        self.latest_freq = _freq(opt["logger"].get("save_latest_freq"))
+        self.val_freq = _freq(_get(opt, "val.val_freq")) if val_store is not None and len(val_store) else None
+        self.metrics = usable_metrics(opt, warn=True) if self.val_freq else {}
+        self.key_metric = _get(opt, "val.key_metric") if self.metrics else None
+        self.best = BestMetrics(self.metrics)
+
+        if seed is not None:
+            torch.manual_seed(int(seed) + self.rank)               # set_random_seed(seed + rank): the weights' initialisation
+        self.net = (net if net is not None else build_network(opt["network_g"])).train().to(self.device)
+        pretrained = _get(opt, "path.pretrain_network_g")
+        resume_state = _get(opt, "path.resume_state")
+        optim = tr["optim_g"]
+        self.optimizer = trainer.make_optimizer(self.net, lr=float(optim["lr"]), weight_decay=float(optim.get("weight_decay", 1e-2)),
+                                                betas=tuple(optim.get("betas", (0.9, 0.999))), capturable=self.graphed)
+        schedulers.set_lr(self.optimizer, [float(optim["lr"])] * len(self.optimizer.param_groups))   # the exact float64 base lr
+        self.scheduler = schedulers.build_scheduler(self.optimizer, tr["scheduler"])
+        self.sampler = EnlargedSampler(len(train_store), self.world, self.rank, ds.get("dataset_enlarge_ratio", 1))
+        if self.sampler.num_samples < self.batch_size:
+            raise ValueError(f"datasets.train.batch_size_per_gpu: {self.batch_size} is more than the {self.sampler.num_samples} "
+                             "samples of an epoch - every batch would be dropped")
+        self.batcher = PairedPatchBatcher(train_store, gt_size=int(ds["gt_size"]), geometric_augs=bool(ds.get("geometric_augs", False)),
+                                          seed=None if seed is None else int(seed) + self.rank)
+        derived = derive_iters(opt, len(train_store), self.world)
+        self.total_iters, self.total_epochs = derived["total_iters"], derived["total_epochs"]
+        self.last_iter = self.total_iters
+        end = self.scheduler.last_iter()
+        if end is not None and end < self.total_iters:
+            self.last_iter = end
+            self._log({"warning": f"train.total_iter is {self.total_iters} but the schedule ends after sum(periods) = {end - 1}: "
+                                  f"iteration {end} is the last one that can run; training ends there with its save and validation"},
+                      logging.WARNING)
+        self.current_iter, self.epoch, self._pos, self._finished = 0, 0, 0, False
+        self._gstep = self._run_graphed = None
+
+        if resume_state:                                           # before anything is captured
+            self._resume(resume_state, pretrained)
+        elif pretrained:
+            trainer.load_network(self.net, pretrained, strict=bool(_get(opt, "path.strict_load", True)))
+
+    # -- resume ---------------------------------------------------------------------------------------------------------------------
+    def _resume(self, path, pretrained):
+        """train.py:159-163 + base_model.py:359-373.  The weights come from path.pretrain_network_g or, without one, from
+        models/net_g_{iter}.pth beside the state's folder (the layout this class writes).  With the state's "recipe" entry the
+        run continues exactly: position inside the epoch and the batcher's random state; without one (a state the reference
+        wrote) the epoch restarts at its first batch with a fresh random state, as in the reference."""
+        state = torch.load(path, map_location="cpu", weights_only=True)
+        epoch, current_iter = trainer.resume_training(state, [self.optimizer], [self.scheduler])
+        weights = pretrained or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "models", f"net_g_{current_iter}.pth")
+        trainer.load_network(self.net, weights, strict=bool(_get(self.opt, "path.strict_load", True)) if pretrained else True)
+        self.epoch, self.current_iter = int(epoch), int(current_iter)
+        extra = state.get("recipe")
+        if extra is not None:
+            self._pos = int(extra["batch"])
+            rng = extra["rng"]
+            self.batcher.rng.setstate((rng[0], tuple(rng[1]), rng[2]))
+        self._log({"resumed": path, "epoch": self.epoch, "iter": self.current_iter, "exact": extra is not None})
+
+    # -- logging / files ------------------------------------------------------------------------------------------------------------
+    def _log(self, record, level=logging.INFO):
+        line = json.dumps(record)
+        os.makedirs(self.out_dir, exist_ok=True)
+        with open(os.path.join(self.out_dir, "train.log"), "a", encoding="utf-8") as f:
+            f.write(line + "\n")
+        LOG.log(level, line)
+
+    def _model_path(self, label):
+        return os.path.join(self.out_dir, "models", f"net_g_{label}.pth")
+
+    def save(self, epoch, current_iter):
+        """model.save(): base_model.py:227-228 and :341-342 name the files."""
+        trainer.save_network(self.net, self._model_path("latest" if current_iter == -1 else current_iter), current_iter, epoch)
+        trainer.save_training_state(os.path.join(self.out_dir, "training_states", f"{current_iter}.state"), epoch, current_iter,
+                                    [self.optimizer], [self.scheduler],
+                                    extra={"batch": self._pos, "rng": self.batcher.rng.getstate()})
+
+    # -- the step ---------------------------------------------------------------------------------------------------------------------
+    def _capture(self, lq, gt):
+        """GraphedTrainStep on (lq, gt) whose three warm-up steps leave no trace (see the module docstring)."""
+        params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        weights = {k: v.detach().clone() for k, v in self.net.state_dict().items()}
+        moments = {p: {k: v.clone() for k, v in st.items() if isinstance(v, torch.Tensor)} for p, st in self.optimizer.state.items()}
+        step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
+        with torch.no_grad():
+            for k, v in self.net.state_dict().items():
+                v.copy_(weights[k])
+            for p in params:
+                saved = moments.get(p)
+                for k, v in self.optimizer.state.get(p, {}).items():
+                    if isinstance(v, torch.Tensor):
+                        v.copy_(saved[k]) if saved is not None else v.zero_()    # no state before: exp_avg, exp_avg_sq, step = 0
+        return step
+
+    def _step(self, rows):
+        if self.graphed:
+            if self._gstep is None:
+                self._gstep = self._capture(*self.batcher.form(rows=rows))
+                self._run_graphed = trainer.graphed_step_with_batcher(self._gstep, self.batcher)
+            return self._run_graphed(rows=rows)
+        lq, gt = self.batcher.form(rows=rows)
+        if self.step_fn is not None:
+            return self.step_fn(lq, gt)
+        return trainer.train_step(self.net, self.optimizer, lq, gt, as_float=False, ssim_weight=self.ssim_weight,
+                                  fft_weight=self.fft_weight)
+
+    # -- validation -------------------------------------------------------------------------------------------------------------------
+    def _enhance_u8(self, lq):
+        """(h, w, 3) uint8 BGR -> the network's output as tensor2img quantises it, (h, w, 3) uint8 BGR."""
+        h, w = lq.shape[:2]
+        if lq.is_cuda:
+            from . import ops
+            return ops.image_post_u8(self.net.test(ops.image_pre_u8(lq, 8, True)), h, w, True)
+        from .inference import check_image_size, to_uint8
+        x = lq.permute(2, 0, 1).flip(0)[None].float() / 255.0
+        out = self.net.test(check_image_size(x, 8))[:, :, :h, :w]
+        return to_uint8(out)[0].flip(0).permute(1, 2, 0).contiguous()
+
+    @torch.no_grad()
+    def score(self):
+        """{metric: mean over val_store}: per pair net.eval(), the uint8 conversion, the arch's test() under no_grad, the
+        tensor2img quantisation, the Y-channel PSNR / SSIM with the metric's crop_border, net.train() (femasr_model.py:187-199,
+        :229-275).  On a GPU the per-image scores are summed on the device in float64, in store order, and read once."""
+        borders = sorted({m["crop_border"] for m in self.metrics.values()})
+        sums, n = {c: None for c in borders}, len(self.val_store)
+        for i in range(n):
+            lq, gt = self.val_store.pair(i)
+            self.net.eval()
+            res = self._enhance_u8(lq)
+            self.net.train()
+            for c in borders:
+                if res.is_cuda:
+                    from . import ops
+                    pair = ops.psnr_ssim_y(res, gt, c, layout="HWC", bgr=True)[0]
+                else:
+                    from .metrics import psnr_ssim_y_cpu
+                    pair = torch.tensor(psnr_ssim_y_cpu(res, gt, c, "HWC", True), dtype=torch.float64)
+                sums[c] = pair if sums[c] is None else sums[c] + pair
+        host = dict(zip(borders, torch.stack([sums[c] for c in borders]).tolist())) if borders else {}
+        return {name: host[m["crop_border"]][0 if m["type"] == "psnr" else 1] / n for name, m in self.metrics.items()}
+
+    def validate(self, current_iter, epoch):
+        """One validation: scores, best bookkeeping, the best checkpoint, one log line.  -> the result dict."""
+        results = self.score()
+        if self.best.update(results, current_iter, self.key_metric):
+            trainer.save_network(self.net, self._model_path(f"best_{current_iter}" if self.key_metric is not None else "best_"),
+                                 current_iter, epoch)
+        self._log({"iter": current_iter, "epoch": epoch, "validation": results,
+                   "best": {k: {"val": r["val"], "iter": r["iter"]} for k, r in self.best.records.items()}})
+        return results
+
+    # -- train.py:197-264 ---------------------------------------------------------------------------------------------------------------
+    def run(self, max_iters=None, on_iter=None):
+        done = 0
+        while not self._finished and self.epoch <= self.total_epochs:
+            self.sampler.set_epoch(self.epoch)
+            batches = self.sampler.batches(self.batch_size)
+            while self._pos < len(batches):
+                if max_iters is not None and done >= max_iters:
+                    return {"iter": self.current_iter, "epoch": self.epoch, "finished": False}
+                if self.current_iter + 1 > self.last_iter:
+                    self._finished = True
+                    break
+                self.current_iter += 1
+                it, epoch = self.current_iter, self.epoch
+                schedulers.update_learning_rate([self.scheduler], [self.optimizer], it, self.warmup_iter)
+                rows = self.batcher.draw(batches[self._pos])
+                self._pos += 1
+                losses = self._step(rows)
+                done += 1
+                if on_iter is not None:
+                    on_iter(it, epoch, schedulers.current_lrs([self.optimizer]), rows, losses)
+                if it % self.print_freq == 0:
+                    self._log({"iter": it, "epoch": epoch, "lrs": schedulers.current_lrs([self.optimizer]),
+                               **trainer.loss_values(losses)})
+                if it % self.save_freq == 0 or (self.latest_freq and it % self.latest_freq == 0):
+                    self.save(epoch, it)
+                if self.val_freq and it % self.val_freq == 0:
+                    self.validate(it, epoch)
+            if self._finished:
+                break
+            self.epoch, self._pos = self.epoch + 1, 0
+        self._finished = True
+        trainer.save_network(self.net, self._model_path("latest"), -1, -1)             # model.save(epoch=-1, current_iter=-1)
+        last = self.validate(self.current_iter, self.epoch) if self.val_freq else None
+        self._log({"end_of_training": True, "iter": self.current_iter})
+        return {"iter": self.current_iter, "epoch": self.epoch, "finished": True, "validation": last}
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------------------
+def load_pairs(folder, device):
+    """DIR/lq/*.npy and DIR/gt/*.npy with equal names, each (h, w, 3) uint8 in BGR order -> DeviceImageStore on `device`."""
+    import glob
+    import numpy as np
+    store = DeviceImageStore(device)
+    names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(folder, "lq", "*.npy")))
+    if not names:
+        raise ValueError(f"{folder}: no lq/*.npy")
+    for name in names:
+        store.add(np.load(os.path.join(folder, "lq", name)), np.load(os.path.join(folder, "gt", name)))
+    return store
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m wave_mamba_amd.recipe", description=__doc__.split("\n")[0])
+    ap.add_argument("-opt", required=True, help="the recipe (YAML)")
+    ap.add_argument("--train-pairs", required=True, help="folder with lq/*.npy and gt/*.npy (uint8, HWC, BGR)")
+    ap.add_argument("--val-pairs", default=None)
+    ap.add_argument("--eager", action="store_true", help="train_step per iteration instead of one graph replay")
+    ap.add_argument("--out-dir", default="experiments")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--max-iters", type=int, default=None, help="pause after this many iterations")
+    args = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    train = load_pairs(args.train_pairs, args.device)
+    val = load_pairs(args.val_pairs, args.device) if args.val_pairs else None
+    opt, _ = load_options(args.opt, num_train=len(train))
+    result = Trainer(opt, train, val, graphed=not args.eager, out_dir=args.out_dir).run(max_iters=args.max_iters)
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -80,8 +80,9 @@ def make_optimizer(net, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.99), capturabl
     updated by the fused multi-tensor implementation (one launch per ~hundred tensors instead of ~10 per tensor
     group); same arithmetic.  capturable: step counters AND the learning rate on the device, for GraphedTrainStep - a
     Python-float lr would be baked into the captured AdamW launch as a kernel scalar and a scheduler (the reference's recipe
-    uses CosineAnnealingRestartCyclicLR, train_wavemamba_uhdll.yml:86-90) would change nothing in the replays; torch's
-    schedulers `fill_()` a tensor lr in place, which the replayed kernel reads."""
+    uses CosineAnnealingRestartCyclicLR, train_wavemamba_uhdll.yml:86-90: schedulers.py) would change nothing in the replays;
+    schedulers.py and torch's own schedulers `fill_()` a tensor lr in place, which the replayed kernel reads (a warm-up or any
+    other direct change goes through schedulers.set_lr, never `group["lr"] = value`)."""
     params = [p for p in net.parameters() if p.requires_grad]
     fused = bool(params) and all(p.is_cuda for p in params)
     kw = {"capturable": True} if capturable else {}
@@ -104,17 +105,17 @@ def wrap_ddp(net, device=None, find_unused_parameters=False, force=False):
                                                      find_unused_parameters=find_unused_parameters)
 
 
-def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None):
+def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None, fft_weight=0.1):
     """One optimize_parameters(): zero_grad, forward, L1 + 0.1*FFT (+ ssim_weight * (1 - SSIM) where a weight is given; the
     loss dict then has "l_ssim", weighted like l_freq), backward (DDP all-reduce), step.
     Returns the reduced losses {name: python float} like the reference's `reduce_loss_dict` (base_model.py:376-401: a log dict
     of floats - callers format / json-dump it).  as_float=False returns 0-dim DEVICE tensors instead: nothing in the step then
     waits for the GPU (a `float()` is a host synchronisation per iteration, under DDP on every rank); `loss_values()` converts
     such a result when it is time to log (the reference logs every `print_freq` iterations).  bench.py and the tools time the
-    step with as_float=False."""
+    step with as_float=False.  `fft_weight`: the recipe's fft_opt.loss_weight (train_wavemamba_uhdll.yml:102-104)."""
     optimizer.zero_grad(set_to_none=True)
     out = net(lq)
-    terms = losses(out, gt, ssim_weight=ssim_weight)
+    terms = losses(out, gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
     _total(terms).backward()
     optimizer.step()
     return reduce_loss_dict({k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}, as_float=as_float)
@@ -127,14 +128,15 @@ class GraphedTrainStep:
     replay costs the host one call.  Single-process training only (GraphedDDPTrainStep is the data-parallel form: a
     DistributedDataParallel reducer cannot run inside a capture); fixed batch shape; `optimizer` must be make_optimizer(..., capturable=True): its learning rate is a device
     tensor, so a torch LR scheduler stepped between replays takes effect (it fills the tensor in place; a float lr is refused -
-    it would be frozen into the graph).  The warm-up steps are real optimizer steps at the optimizer's current lr.
+    it would be frozen into the graph).  The warm-up steps are real optimizer steps at the optimizer's current lr
+    (recipe.Trainer undoes them in place, so that every iteration of its loop is one step of the recipe).
 
         step = GraphedTrainStep(net, optimizer, lq0, gt0)          # 3 eager warm-up steps on (lq0, gt0), then the capture
         losses = step(lq, gt)                                      # copies the batch into the graph's input buffers, replays
     Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`) as 0-dim device tensors of the step just replayed
     (loss_values() to log them)."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep: single-process training only (under torch.distributed: GraphedDDPTrainStep)")
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
@@ -143,11 +145,12 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: the optimizer's lr must be a device tensor (make_optimizer(net, capturable=True)): "
                                "a float lr is frozen into the captured graph and learning-rate schedules would be ignored")
         self.lq, self.gt = lq.clone(), gt.clone()
+        self.lr_tensors = [g["lr"] for g in optimizer.param_groups]   # what the captured AdamW reads: fill_() them, never rebind g["lr"]
         side = torch.cuda.Stream(lq.device)
         side.wait_stream(torch.cuda.current_stream(lq.device))
         with torch.cuda.stream(side):                              # warm-up off the capture's stream (allocator pools, library set-up)
             for _ in range(warmup):
-                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight)
+                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight, fft_weight=fft_weight)
         torch.cuda.current_stream(lq.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -159,7 +162,7 @@ class GraphedTrainStep:
             mode = {"capture_error_mode": "thread_local"}
         with torch.cuda.graph(self.graph, **mode):
             out = net(self.lq)
-            terms = losses(out, self.gt, ssim_weight=ssim_weight)
+            terms = losses(out, self.gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
             _total(terms).backward()
             optimizer.step()
         self.losses = {k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}
@@ -373,24 +376,39 @@ def load_network(net, path, strict=True, param_key="params", weights_only=True):
     return list(res.missing_keys), list(res.unexpected_keys), skipped
 
 
-def save_training_state(path, epoch, current_iter, optimizers, schedulers=()):
+def save_training_state(path, epoch, current_iter, optimizers, schedulers=(), extra=None):
     """`{'epoch', 'iter', 'optimizers': [...], 'schedulers': [...]}` (base_model.py:328-357); nothing is written for
-    current_iter == -1, and only rank 0 writes."""
+    current_iter == -1, and only rank 0 writes.  `extra` (anything torch.load(weights_only=True) reads back) is stored under one
+    more key, "recipe": recipe.Trainer keeps its position inside the epoch and the batcher's random state there; the reference's
+    resume_training reads the four keys above and ignores the rest."""
     if current_iter == -1 or (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0):
         return None
-    _atomic_save({"epoch": epoch, "iter": current_iter, "optimizers": [o.state_dict() for o in optimizers],
-                  "schedulers": [s.state_dict() for s in schedulers]}, path)
+    state = {"epoch": epoch, "iter": current_iter, "optimizers": [o.state_dict() for o in optimizers],
+             "schedulers": [s.state_dict() for s in schedulers]}
+    if extra is not None:
+        state["recipe"] = extra
+    _atomic_save(state, path)
     return path
 
 
 def resume_training(path_or_state, optimizers, schedulers=(), weights_only=True):
-    """base_model.py:359-373.  Returns (epoch, iter).  `weights_only` as in load_network."""
+    """base_model.py:359-373.  Returns (epoch, iter).  `weights_only` as in load_network.
+    A param group whose lr is a DEVICE tensor (make_optimizer(capturable=True)) keeps that tensor: optimizer.load_state_dict
+    replaces the groups with the saved ones, whose lr is a CPU tensor (this package's files, loaded to the CPU) or a float (the
+    reference's) - GraphedTrainStep refuses both, and a graph captured earlier would go on reading the old tensor.  The tensor is
+    filled with the loaded value (its float64 mirror "lr_host" of schedulers.set_lr where the state has one) and put back."""
     st = path_or_state if isinstance(path_or_state, dict) else torch.load(path_or_state, map_location="cpu",
                                                                             weights_only=weights_only)
     if len(st["optimizers"]) != len(optimizers) or len(st["schedulers"]) != len(schedulers):
         raise ValueError("resume_training: optimizer / scheduler count differs from the saved state")
     for o, s in zip(optimizers, st["optimizers"]):
+        kept = [g["lr"] if isinstance(g["lr"], torch.Tensor) and g["lr"].is_cuda else None for g in o.param_groups]
         o.load_state_dict(s)
+        for g, lr in zip(o.param_groups, kept):
+            if lr is not None:
+                value = float(g["lr_host"]) if "lr_host" in g else float(g["lr"])
+                lr.fill_(value)
+                g["lr"], g["lr_host"] = lr, value
     for o, s in zip(schedulers, st["schedulers"]):
         o.load_state_dict(s)
     return st["epoch"], st["iter"]
