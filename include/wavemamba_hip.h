@@ -221,6 +221,26 @@ int wm_lfss_in_conv_band_rows(int B, int H, int W);
 int wm_lfss_out_conv_fwd(const void* f, const float* conv2_weight, const float* conv2_bias, const float* tok1,
                          const float* conv3_weight, const float* conv3_bias, const float* skip_scale2, float* out,
                          int out_nchw, int B, int H, int W, int C, int plane_dtype, void* stream);
+/* The gated ffn without f (conv1's output planes) in HBM: wm_lfss_mid_rz_fwd + wm_lfss_out_conv_fwd as
+ *   wm_lfss_mid_rz_tok_fwd  wm_lfss_mid_rz_fwd that ends at tok1 (no ln_2, conv1 or f; bit-identical tok1).  C == 32, ny == 4 and
+ *                           plane_dtype == WM_F32 only (WM_EUNSUPPORTED otherwise).
+ *   wm_lfss_ffn_fwd         tok1 (B, L, C) -> out = tok1 * skip_scale2 + conv3(gelu(fc[:C]) * fc[C:]), fc = conv2(conv1(ln_2(tok1)))
+ *                           (wavemamba_arch.py:226-230, :526) in one kernel: f on the depth-wise 3x3's one-pixel halo is recomputed
+ *                           from tok1, never stored (-700 B per position).  Bit-identical to the pair on fp32 planes.  C == 32,
+ *                           plane_dtype == WM_F32, W % 32 == 0 and H W <= 2^23 only (WM_EUNSUPPORTED otherwise: use the pair).
+ *                           conv2_bias may be NULL; out (B, L, C) or (B, C, H, W) when out_nchw, aliases no input.  band_rows: output
+ *                           rows per band of the row walk, 0 = the entry's plan.
+ *   wm_lfss_ffn_band_rows   host only - that plan at this shape (every band recomputes two more rows of f); negative status outside
+ *                           the domain. */
+int wm_lfss_mid_rz_tok_fwd(const void* ysum, int ny, int64_t ystride, const float* tok, int tok_nchw, const float* ln1_w,
+                           const float* ln1_b, float ln1_eps, const float* in_proj_weight, const float* out_norm_w,
+                           const float* out_norm_b, float out_norm_eps, const float* out_proj_weight, const float* skip_scale,
+                           float* tok1, int B, int64_t L, int C, int plane_dtype, void* stream);
+int wm_lfss_ffn_fwd(const float* tok1, const float* ln2_w, const float* ln2_b, float ln2_eps, const float* conv1_weight,
+                    const float* conv1_bias, const float* conv2_weight, const float* conv2_bias, const float* conv3_weight,
+                    const float* conv3_bias, const float* skip_scale2, float* out, int out_nchw, int B, int H, int W, int C,
+                    int plane_dtype, int band_rows, void* stream);
+int wm_lfss_ffn_band_rows(int B, int H, int W);
 
 /* --------------------------------------------------------------------------------------------
  * LayerNorm2d of the HFE branch (first "next" row): per-pixel LayerNorm over the C

@@ -41,7 +41,10 @@ SIGNATURES = {
     "wm_lfss_in_conv_band_rows": (_i, [_i, _i, _i]),
     "wm_lfss_mid_rz_fwd": (_i, [_p, _i, _i64, _p, _i, _p, _p, _c.c_float, _p, _p, _p, _c.c_float, _p, _p, _p, _p, _c.c_float, _p, _p,
                                _p, _p, _i, _i64, _i, _i, _p]),
-    "wm_lfss_mid_fwd": (_i, [_p, _i, _i64, _p, _p, _i, _p, _p, _c.c_float, _p, _p, _p, _p, _c.c_float, _p, _p, _p, _p,
+    "wm_lfss_mid_rz_tok_fwd": (_i, [_p, _i, _i64, _p, _i, _p, _p, _c.c_float, _p, _p, _p, _c.c_float, _p, _p, _p, _i, _i64, _i, _i, _p]),
+    "wm_lfss_ffn_fwd": (_i, [_p, _p, _p, _c.c_float] + [_p] * 8 + [_i] * 7 + [_p]),
+    "wm_lfss_ffn_band_rows": (_i, [_i, _i, _i]),
+    "wm_lfss_mid_fwd": (_i,[_p, _i, _i64, _p, _p, _i, _p, _p, _c.c_float, _p, _p, _p, _p, _c.c_float, _p, _p, _p, _p,
                              _i, _i64, _i, _i, _p]),
     "wm_lfss_out_fwd": (_i, [_p] * 6 + [_i, _i, _i64, _i, _i, _p]),
     "wm_lfss_out_conv_fwd": (_i, [_p] * 8 + [_i] * 6 + [_p]),

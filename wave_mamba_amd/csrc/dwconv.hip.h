@@ -26,6 +26,15 @@ __device__ __forceinline__ float dpp_from_upper_lane(float own_if_last, float v)
                                                                  0x130 /* wave_shl:1 */, 0xf, 0xf, false));
 }
 
+// the same shifts with ZERO entering at the wave's first / last lane (bound_ctrl): no previous value to keep, so the move folds into
+// the instruction that consumes it (v_fmac_f32_dpp)
+__device__ __forceinline__ float dpp_zero_from_lower_lane(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float dpp_zero_from_upper_lane(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
+}
+
 // `bytes` of memory from `p` as a raw buffer (the one place the descriptor's flags word is written): a load or store whose offset is
 // >= bytes reads zero / is dropped
 template <typename TP>

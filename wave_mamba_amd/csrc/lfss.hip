@@ -227,7 +227,67 @@ int wm_lfss_mid_rz_fwd(const void* ysum_, int ny, int64_t ystride, const float* 
                                    conv1_bias, tok1, f_, B, L, plane_dtype, (hipStream_t)stream);
 }
 
-int wm_lfss_out_fwd(const void* fc_, const float* tok1, const float* conv3_weight, const float* conv3_bias,
+// wm_lfss_mid_rz_fwd that ends at tok1 (no ln_2, no conv1, no f): the middle kernel in front of wm_lfss_ffn_fwd, which recomputes f
+// from tok1.  Only the form that path needs: C == 32, the four directions' outputs (ny == 4), fp32 planes.  tok1 is bit-identical to
+// wm_lfss_mid_rz_fwd's.
+int wm_lfss_mid_rz_tok_fwd(const void* ysum_, int ny, int64_t ystride, const float* tok, int tok_nchw, const float* ln1_w,
+                           const float* ln1_b, float ln1_eps, const float* in_proj_weight, const float* out_norm_w,
+                           const float* out_norm_b, float out_norm_eps, const float* out_proj_weight, const float* skip_scale,
+                           float* tok1, int B, int64_t L, int C, int plane_dtype, void* stream) {
+    if (B < 0 || L < 0) return WM_EINVAL;
+    if (C != 32 || ny != 4 || plane_dtype != WM_F32) return WM_EUNSUPPORTED;
+    if (B == 0 || L == 0) return WM_OK;
+    if (!ysum_ || !tok || !ln1_w || !ln1_b || !in_proj_weight || !out_norm_w || !out_norm_b || !out_proj_weight || !skip_scale || !tok1)
+        return WM_ENULL;
+    if ((!tok_nchw && !aligned16(tok)) || !aligned16(tok1)) return WM_EALIGN;
+    const Lfss32Grid g = lfss32_grid(B, L, 1024 * WM_LFSS_MID_RZ_WAVES);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(9, st);
+    hipLaunchKernelGGL((lfss_mid_mfma_kernel<4, float, true, false>), g.grid, dim3(256), 0, st, (const float*)ysum_, (long long)ystride,
+                       (const float*)nullptr, tok, tok_nchw, out_norm_w, out_norm_b, out_norm_eps, out_proj_weight, skip_scale,
+                       (const float*)nullptr, (const float*)nullptr, 0.0f, (const float*)nullptr, (const float*)nullptr, tok1,
+                       (float*)nullptr, B, (long long)L, g.ngl, g.ngroups, g.gpw, ln1_w, ln1_b, ln1_eps, in_proj_weight);
+    return launch_status();
+}
+
+// The gated ffn behind wm_lfss_mid_rz_tok_fwd in one kernel (lfss_ffn_mfma_kernel): ln_2 -> conv1 -> depth-wise 3x3 -> GELU gate ->
+// conv3 -> second skip connection, f and fc never stored.  C == 32, fp32 planes, W % 32 == 0 and at most 2^23 positions per image
+// (32-bit byte offsets inside an image's output).  WM_EUNSUPPORTED otherwise: callers keep wm_lfss_mid_rz_fwd + wm_lfss_out_conv_fwd.
+static bool lfss_ffn_domain(int H, int W, int C, int plane_dtype) {
+    return C == 32 && plane_dtype == WM_F32 && W % 32 == 0 && (long long)H * W <= (1ll << 23);
+}
+
+int wm_lfss_ffn_band_rows(int B, int H, int W) {
+    if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
+    if (!lfss_ffn_domain(H, W, 32, WM_F32)) return WM_EUNSUPPORTED;
+    return lfss_ffn_band_rows(B, H, W);
+}
+
+int wm_lfss_ffn_fwd(const float* tok1, const float* ln2_w, const float* ln2_b, float ln2_eps, const float* conv1_weight,
+                    const float* conv1_bias, const float* conv2_weight, const float* conv2_bias, const float* conv3_weight,
+                    const float* conv3_bias, const float* skip_scale2, float* out, int out_nchw, int B, int H, int W, int C,
+                    int plane_dtype, int band_rows, void* stream) {
+    if (B < 0 || H < 0 || W < 0 || band_rows < 0) return WM_EINVAL;
+    if (!lfss_ffn_domain(H, W, C, plane_dtype)) return WM_EUNSUPPORTED;
+    if (B == 0 || H == 0 || W == 0) return WM_OK;
+    if (!tok1 || !ln2_w || !ln2_b || !conv1_weight || !conv1_bias || !conv2_weight || !conv3_weight || !conv3_bias || !skip_scale2 || !out)
+        return WM_ENULL;
+    if (!aligned16(tok1) || (!out_nchw && !aligned16(out))) return WM_EALIGN;
+    const int nstrips = (W + kFfnCols - 1) / kFfnCols, rb = band_rows ? band_rows : lfss_ffn_band_rows(B, H, W), nbands = (H + rb - 1) / rb;
+    const long long nwalks = (long long)B * nbands * nstrips;
+    const dim3 grid((unsigned)((nwalks + 31) / 32 * 8));         // four walks per workgroup, a multiple of 8 workgroups (XCD runs)
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(11, st);
+    if (out_nchw)
+        hipLaunchKernelGGL(lfss_ffn_mfma_kernel<true>, grid, dim3(256), 0, st, tok1, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
+                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, nstrips, nbands, rb, nwalks);
+    else
+        hipLaunchKernelGGL(lfss_ffn_mfma_kernel<false>, grid, dim3(256), 0, st, tok1, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
+                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, nstrips, nbands, rb, nwalks);
+    return launch_status();
+}
+
+int wm_lfss_out_fwd(const void* fc_,const float* tok1, const float* conv3_weight, const float* conv3_bias,
                     const float* skip_scale2, float* out, int out_nchw, int B, int64_t L, int C, int plane_dtype, void* stream) {
     if (B < 0 || L < 0) return WM_EINVAL;
     if (plane_dtype != WM_F32 && !(plane_dtype == WM_BF16 && C == 32)) return WM_EUNSUPPORTED;

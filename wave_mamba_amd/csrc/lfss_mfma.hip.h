@@ -18,7 +18,7 @@
 // (DESIGN.md 4): loads are issued in explicit batches ahead of their use and ahead of the group's stores.
 // Reference: basicsr/archs/wavemamba_arch.py :491-494 (SS2D tail), :525-526 (LFSSBlock), :226-230 (ffn).
 //
-// The six kernels are built from these pieces (each written once, with its layout comment):
+// The seven kernels are built from these pieces (each written once, with its layout comment):
 //   group_pos                          group number -> batch image and first position
 //   load_tile32 / store_tile32         a 32-position tile of tokens or planes <-> accumulator layout
 //   tile_normalise, xhalf_sum          LayerNorm statistics over a tile's 16 + 16 registers
@@ -32,7 +32,7 @@
 //   plane_rsrc, buf_ld, load_dw_taps             memory / one channel plane as a raw buffer (raw_rsrc: dwconv.hip.h); a channel's taps from LDS
 //   dw_taps9, dw_taps3 (dwconv.hip.h)  the depth-wise sum in the depth-wise kernel's own order; one kernel row of it (lfss_in_conv
 //                                      continues three output rows' chains with each x row)
-//   lfss_in_conv_band_rows             rows per band of lfss_in_conv (host)
+//   lfss_in_conv_band_rows, lfss_ffn_band_rows   rows per band of lfss_in_conv / lfss_ffn (host)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "haar.hip.h"          // bf16_t, ld1 / st1 (fp32 and bf16 overloads)
@@ -246,7 +246,9 @@ __device__ __forceinline__ void store_rows64(TP* __restrict__ plane0 /* channel 
 // A operands (W_in rows D.. x ln_1.weight), the same normalised tile as B operands, the same matrix-instruction order and bias
 // start as lfss_in_mfma_kernel - bit-identical z in fp32 storage - with the output ROWS permuted so that accumulator
 // register i of row block mt IS channel 2 (16 mt + i) + h: the layout the out_norm'ed y has after its half-wave swap.
-template <int NY, typename TP = float, bool RZ = false>
+// FOUT = false: the kernel ends at tok1 - no ln_2, no conv1, no f (lfss_ffn_mfma_kernel recomputes f from tok1); the ln_2 / conv1
+// arguments are not read.  Nothing before the tok1 store differs: tok1 is bit-identical.
+template <int NY, typename TP = float, bool RZ = false, bool FOUT = true>
 __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES) void lfss_mid_mfma_kernel(
     const TP* __restrict__ ysum, long long ystride, const TP* __restrict__ z, const float* __restrict__ tok, int tok_nchw,
     const float* __restrict__ on_w, const float* __restrict__ on_b, float on_eps,
@@ -259,9 +261,9 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
     static_assert(NY == 1 || NY == 4, "merged or four separate core outputs");
     constexpr int C = 32, D = 64;
     __shared__ __attribute__((aligned(16))) float s_skip[C];
-    __shared__ __attribute__((aligned(16))) float s_b1[D];
+    __shared__ __attribute__((aligned(16))) float s_b1[FOUT ? D : 4];
     __shared__ __attribute__((aligned(16))) float s_Aout[(D / 2) * 64];          // 32 operands x 64 lanes
-    __shared__ __attribute__((aligned(16))) float s_A1[2 * (C / 2) * 64];        // 2 row blocks x 16 operands
+    __shared__ __attribute__((aligned(16))) float s_A1[FOUT ? 2 * (C / 2) * 64 : 4];   // 2 row blocks x 16 operands
     __shared__ __attribute__((aligned(16))) float s_Az[RZ ? 2 * (C / 2) * 64 : 4];   // RZ: the gate's 2 row blocks x 16 operands
     __shared__ __attribute__((aligned(16))) float s_bz[RZ ? D : 4];             // RZ: [half h][row block][register]
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
@@ -278,12 +280,14 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
         }
     }
     if (threadIdx.x < C) s_skip[threadIdx.x] = skip1[threadIdx.x];
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + D) {
-        const int m = threadIdx.x - 64;
-        s_b1[m] = folded_bias(W1, m, ln2_b, b1[m]);
+    if constexpr (FOUT) {
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + D) {
+            const int m = threadIdx.x - 64;
+            s_b1[m] = folded_bias(W1, m, ln2_b, b1[m]);
+        }
+        stage_aop_rows<2>(s_A1, W1, ln2_w);
     }
     stage_aop<D / 2>(s_Aout, [=](int j, int l) { return W_out[(l & 31) * D + 2 * j + (l >> 5)]; });
-    stage_aop_rows<2>(s_A1, W1, ln2_w);
     __syncthreads();
 
     const long long g0 = ((long long)blockIdx.x * 4 + wv) * gpw;
@@ -401,10 +405,11 @@ __global__ __launch_bounds__(256, RZ ? WM_LFSS_MID_RZ_WAVES : WM_LFSS_MID_WAVES)
                 tt[t][4 * gq + 3] = fmaf(tt[t][4 * gq + 3], sk.w, acc[t][4 * gq + 3]);
             }
             if (pos < L) store_tile32(tok1, false, b, pos, L, h, tt[t]);
-            tile_normalise(tt[t], ln2_eps);
+            if constexpr (FOUT) tile_normalise(tt[t], ln2_eps);
         }
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
+            if constexpr (!FOUT) break;
             lfss_v16f a[2];
             acc_rows(s_b1 + 32 * mt, h, a[0]);
             a[1] = a[0];
@@ -918,6 +923,174 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
                 }
             }
         }
+    }
+}
+
+// ---- lfss_ffn: tok1 -> tok2; f = conv1(ln_2(tok1)) never reaches memory ---------------------------------------------------------
+// The gated ffn in one kernel (reference :226-230 behind ln_2, and the block's second skip connection :526).  lfss_mid wrote f (256 B
+// per position) and lfss_out_conv read it back on a one-pixel halo (486 B by the counters); f is a pointwise function of tok1, which
+// lfss_out_conv reads anyway, so here the halo is RECOMPUTED (pw_dw_kernel's layout on the fp32 matrix cores):
+//   * a wave owns a strip of kFfnCols = 30 output columns - its 32 pixel lanes are 32 consecutive image columns, one halo column each
+//     side, h = lane >> 5 is the k-half - x a band of `rb` output rows (lfss_ffn_band_rows), and walks the band's rb + 2 rows of tok1;
+//   * per row: load_tile32 -> tile_normalise -> both row blocks of conv1 through mfma_rows with lfss_mid's A operands, K order and bias
+//     start (identical f bits): register i of block mt in lane (n, h) is channel 32 mt + acc_chan(i, h) of the lane's OWN pixel;
+//   * the taps: horizontal neighbours are the adjacent lanes (DPP; what the first / last pixel lane of a half takes is another
+//     channel's - those lanes are the halo columns and store nothing), the vertical direction is three running chains per channel
+//     (dw_taps3, as lfss_in_conv): each fc value is dw_taps9's one fmaf chain, zero padding enters as zero operands;
+//   * the GLU pair (c, c + 32) is register i of block 0 and of block 1 in the same lane, and the 16 gated values are conv3's B
+//     operands of K-steps 0 .. 15 as they stand (stage_W3's order, lfss_out's): no LDS exchange, no swap, no barrier in the row loop;
+//   * skip_add with the row's tok1 tile, RELOADED a row later (a cache hit) rather than kept: the row's registers take the load two
+//     rows ahead.
+// Every element takes the pair's arithmetic path: tok2 is BIT-IDENTICAL to wm_lfss_mid_rz_fwd's f stage + wm_lfss_out_conv_fwd on fp32
+// planes.  No branch around a memory operation in the row loop: loads come from clamped addresses, stores are raw buffer stores whose
+// offset is out of range for the halo lanes, columns past the image and rows outside the band.
+constexpr int kFfnCols = 30;                                // output columns per strip
+constexpr int kFfnMinBand = 4, kFfnMaxBand = 64;            // output rows per band (two more rows are recomputed per band)
+// rows per band.  A workgroup is four strips at two waves per SIMD, so the chip holds 512 workgroups at a time and a launch lasts about
+// rounds x (rb + 2 rows + one of prologue): the rb with the smallest such product (UHD level 1: 34 rows, 2048 walks - one round).
+inline int lfss_ffn_band_rows(int B, int H, int W) {
+    const long long nstrips = (W + kFfnCols - 1) / kFfnCols;
+    int rb = kFfnMinBand;
+    long long best = -1;
+    for (int cand = kFfnMinBand; cand <= kFfnMaxBand; ++cand) {
+        const long long nb = (H + cand - 1) / cand, wgs = ((long long)B * nstrips * nb + 3) / 4;
+        const long long cost = ((wgs + 511) / 512) * (cand + 3);
+        if (best < 0 || cost < best) { best = cost; rb = cand; }
+    }
+    return rb;
+}
+
+typedef unsigned lfss_v4u __attribute__((ext_vector_type(4)));
+
+template <bool NCHW /* the output's layout; tok1 is token rows */>
+__global__ __launch_bounds__(256, 2) void lfss_ffn_mfma_kernel(
+    const float* __restrict__ tok1, const float* __restrict__ ln2_w, const float* __restrict__ ln2_b, float ln2_eps,
+    const float* __restrict__ W1 /*(D, C)*/, const float* __restrict__ b1, const float* __restrict__ cw /*(D, 3, 3)*/,
+    const float* __restrict__ cbias /*(D) or null*/, const float* __restrict__ W3 /*(C, C)*/, const float* __restrict__ b3,
+    const float* __restrict__ skip2, float* __restrict__ out, int B, int H, int W, int nstrips, int nbands, int rb, long long nwalks) {
+    constexpr int C = 32, D = 64;
+    __shared__ __attribute__((aligned(16))) float s_b1[D];
+    __shared__ __attribute__((aligned(16))) float s_b3[C];
+    __shared__ __attribute__((aligned(16))) float s_skip[C];
+    __shared__ __attribute__((aligned(16))) float s_A1[2 * (C / 2) * 64];        // conv1: 2 row blocks x 16 operands
+    __shared__ __attribute__((aligned(16))) float s_A3[(C / 2) * 64];            // conv3: 16 operands, lfss_out's K order
+    __shared__ __attribute__((aligned(16))) float s_cw[D * 12];                  // [channel][9 taps | bias | 0 0]
+    const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // workgroup q runs on XCD q mod 8 (each with a private L2): every XCD gets a contiguous run of walks (the grid is a multiple of 8)
+    const long long blk = (long long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const bool live = blk * 4 + wv < nwalks;                     // (a wave past the last walk: the last walk's addresses, no loop)
+    const long long wk = live ? blk * 4 + wv : nwalks - 1;       // walk = (batch, band, strip), strips fastest
+    const int strip = (int)(wk % nstrips);
+    const int band = (int)((wk / nstrips) % nbands);
+    const long long b = wk / ((long long)nstrips * nbands);
+    const long long L = (long long)H * W;
+    const int col = strip * kFfnCols - 1 + n;                    // the lane's image column (pixel lanes 0 and 31: the halo columns)
+    const int colc = min(max(col, 0), W - 1);
+    const bool colin = col >= 0 && col < W;
+    const bool st_ok = n >= 1 && n <= kFfnCols && col < W;
+    const int r0 = band * rb, r_end = min(H, r0 + rb);
+    // the image's output as one raw buffer of 128 L bytes (L <= 2^23); an offset >= nrec is dropped
+    const unsigned plane_bytes = (unsigned)(L * 4), nrec = 32u * plane_bytes;
+    const __amdgpu_buffer_rsrc_t rs = raw_rsrc(out + b * C * L, (int)nrec);
+    const unsigned lane_off = NCHW ? 4u * h * plane_bytes + 4u * colc : 128u * colc + 16u * h;
+    const unsigned row_bytes = NCHW ? 4u * W : 128u * W;
+
+    auto load_row = [&](int rho, float (&nx)[16]) {              // clamped: a row or column outside the image is masked when consumed
+        load_tile32(tok1, false, b, (long long)min(max(rho, 0), H - 1) * W + colc, L, h, nx);
+    };
+    float nxa[16], nxb[16];
+    load_row(r0 - 1, nxa);                                       // on their way while the workgroup stages its constants
+    __builtin_amdgcn_sched_barrier(0);
+    load_row(r0, nxb);
+    __builtin_amdgcn_sched_barrier(0);
+
+    if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + D) {
+        const int m = threadIdx.x - 64;
+        s_b1[m] = folded_bias(W1, m, ln2_b, b1[m]);
+    }
+    stage_aop_rows<2>(s_A1, W1, ln2_w);                          // lfss_mid's conv1 operands
+    stage_W3(s_A3, W3);                                          // lfss_out's K order: bit-identical sums
+    stage_dw_taps(s_cw, cw, cbias);
+    __syncthreads();
+    if (!live) return;
+
+    // the chains of output rows r + 1 (P0: bias + kernel row 0 so far) and r (P1: + kernel row 1) after f row r, of channel
+    // 32 mt + acc_chan(i, h) at [16 mt + i]
+    float P0[32], P1[32];
+#pragma unroll
+    for (int q = 0; q < 32; ++q) { P0[q] = 0.0f; P1[q] = 0.0f; }   // (the band's first two rows end and continue rows above it: not stored)
+
+    // tok1 row rho (in `nx`) enters the window: its f row is formed, output row rho - 1 leaves
+    auto step = [&](int rho, float (&nx)[16]) {
+        int lo = lane, ho = h;                                   // opaque: what is read from LDS through them stays in the loop
+        asm volatile("" : "+v"(lo), "+v"(ho));
+        float a[16];                                             // the row's normalised tokens: conv1's B operands
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = nx[i];
+        tile_normalise(a, ln2_eps);
+        float tk[16];
+        load_row(rho - 1, tk);                                   // the leaving row's tokens again, for its skip connection
+        __builtin_amdgcn_sched_barrier(0);
+        load_row(rho + 2, nx);                                   // two rows ahead, ahead of this row's stores
+        __builtin_amdgcn_sched_barrier(0);
+        lfss_v16f fa[2][1];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            acc_rows(s_b1 + 32 * mt, ho, fa[mt][0]);
+            mfma_rows<C / 8>(s_A1, 4 * mt, lo, [=](int j, int) { return a[j]; }, fa[mt]);
+        }
+        const bool keep = colin && rho >= 0 && rho < H;          // else: zero padding
+        const bool orow = rho - 1 >= r0 && rho - 1 < r_end;      // (wave-uniform)
+        const unsigned voff = (st_ok && orow) ? lane_off + (unsigned)(rho - 1) * row_bytes : nrec;
+        float g[16];                                             // gelu(gate) * value of channel acc_chan(i, h): conv3's B operands
+        // (two forms measured the same and were not kept: the next pair's taps read from LDS under this pair's chains - 36 more
+        // registers; and a software pipeline with row rho + 1's conv1 and this row's conv3 K-steps issued between the pairs' chains - 254
+        // registers.  The row's ~1540 vector instructions are what the kernel waits for, not its matrix time or its LDS reads.)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            float fc[2];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const int q = 16 * mt + i;
+                const float xm = keep ? fa[mt][0][i] : 0.0f;
+                const float t3[3] = {dpp_zero_from_lower_lane(xm), xm, dpp_zero_from_upper_lane(xm)};
+                float w[10];
+                load_dw_taps(s_cw, 32 * mt + acc_chan(i, ho), w);
+                fc[mt] = dw_taps3(P1[q], w + 6, t3);
+                P1[q] = dw_taps3(P0[q], w + 3, t3);
+                P0[q] = dw_taps3(w[9], w, t3);
+                // (pinned here: the two chains are read in the next row only, and the optimiser otherwise sinks them below the stores)
+                asm volatile("" : "+v"(P0[q]), "+v"(P1[q]));
+            }
+            g[i] = gelu_erf(fc[0]) * fc[1];
+            asm volatile("" : "+v"(g[i]));                       // (formed here: left alone, erf's tail and the product sink to the MFMAs)
+            __builtin_amdgcn_sched_barrier(0);                  // one GLU pair's taps and neighbours in registers at a time
+        }
+        lfss_v16f acc[1];
+        acc_rows(s_b3, ho, acc[0]);
+        mfma_rows<C / 8>(s_A3, 0, lo, [=](int j, int) { return g[j]; }, acc);
+        skip_add(s_skip, ho, acc[0], tk);
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            if constexpr (NCHW) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(tk[4 * gq + i]), rs, (int)voff, (int)((8 * gq + i) * plane_bytes), 0);
+            } else {
+                const lfss_v4u v = {__float_as_uint(tk[4 * gq]), __float_as_uint(tk[4 * gq + 1]), __float_as_uint(tk[4 * gq + 2]),
+                                    __float_as_uint(tk[4 * gq + 3])};
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)voff, 32 * gq, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+#pragma unroll 1
+    for (int rho = r0 - 1; rho <= r_end; rho += 2) {             // (an odd count's last step is one row past the band: nothing stored)
+        step(rho, nxa);
+        step(rho + 1, nxb);
     }
 }
 

@@ -617,6 +617,22 @@ _FUSE_IN_CONV_MIN_POSITIONS = 544 * 960
 # The gate z = in_proj(ln_1(x))[D:] recomputed by lfss_mid from the tokens instead of written by lfss_in and read back
 # (512 of the block's 3456 B per position; bit-identical in fp32 planes: tests/test_gpu_parity.py).  0: round-3 data flow.
 _RECOMPUTE_Z = True
+# ln_2 -> conv1 -> depth-wise 3x3 -> GELU gate -> conv3 -> skip as ONE kernel behind a middle kernel that ends at tok1
+# (wm_lfss_mid_rz_tok_fwd + wm_lfss_ffn_fwd: f = conv1(ln_2(tok1)) never reaches HBM; bit-identical on fp32 planes).  It needs the
+# recomputed gate, fp32 planes and inference.  False: wm_lfss_mid_rz_fwd + wm_lfss_out_conv_fwd, tests and tools.
+_FUSE_FFN = True
+# The maps the new pair takes: those the entry supports with at least as many positions PER IMAGE as the smallest map at which it
+# measured faster than the old pair (tools/bench_lfss_ffn.py, profiles/lfss_ffn/per_call.txt; only B = 1 was measured): the new pair's
+# slowest repetition is below the old pair's fastest at UHD level 1 (1088 x 1920, about 0.13 ms per call) and level 2 (544 x 960,
+# about 0.02 ms); at level 3 (272 x 480) the new pair is 0.01 ms SLOWER - 1088 four-row walks fill half the chip - and the old pair
+# stays.  No map between levels 3 and 2 was measured: those keep the old pair until one is.
+_FUSE_FFN_MIN_POSITIONS = 544 * 960
+
+
+def _fuse_ffn_map(B, H, W):
+    """Maps on which lfss_block_forward takes wm_lfss_mid_rz_tok_fwd + wm_lfss_ffn_fwd: inside the entry's domain and, per image, at
+    least as large as the smallest map at which the pair measured faster than wm_lfss_mid_rz_fwd + wm_lfss_out_conv_fwd."""
+    return B > 0 and W % 32 == 0 and _FUSE_FFN_MIN_POSITIONS <= H * W <= (1 << 23)
 
 
 def _fuse_in_conv_map(B, H, W):
@@ -671,12 +687,18 @@ def lfss_block_forward(tok, x_size, blk, tok_nchw=False, out_nchw=False):
     ny = 4
     y4 = _ss2d_core_fwd([xc] + core_w, merged=0, prepared=_ss2d_core_prepared(core_params))
     tok1 = torch.empty((B, L, C), dtype=torch.float32, device=dev)
+    out = torch.empty((B, C, H, W) if out_nchw else (B, L, C), dtype=torch.float32, device=dev)
+    # the gated ffn as one kernel: f (conv1's output) never reaches HBM
+    if rz and _FUSE_FFN and pd == torch.float32 and _fuse_ffn_map(B, H, W):
+        _launch(dev, "wm_lfss_mid_rz_tok_fwd", y4[0], ny, B * D * L, tok, int(tok_nchw), *ln1, *mid[:5], tok1, B, L, C, code)
+        _launch(dev, "wm_lfss_ffn_fwd", tok1, *mid[5:], _w(ff.conv2.weight), None if ff.conv2.bias is None else _w(ff.conv2.bias),
+                *tail, out, int(out_nchw), B, H, W, C, code, 0)
+        return out
     f = torch.empty((B, D, H, W), dtype=pd, device=dev)
     if rz:
         _launch(dev, "wm_lfss_mid_rz_fwd", y4[0], ny, B * D * L, tok, int(tok_nchw), *ln1, *mid, tok1, f, B, L, C, code)
     else:
         _launch(dev, "wm_lfss_mid_fwd", y4[0], ny, B * D * L, z, tok, int(tok_nchw), *mid, tok1, f, B, L, C, code)
-    out = torch.empty((B, C, H, W) if out_nchw else (B, L, C), dtype=torch.float32, device=dev)
     if fuse_out:
         _launch(dev, "wm_lfss_out_conv_fwd", f, *conv2, tok1, *tail, out, int(out_nchw), B, H, W, C, code)
         return out
