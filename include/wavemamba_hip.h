@@ -128,9 +128,16 @@ int wm_selscan_bwd(const float* u, const float* delta, const float* A, const flo
  *   Supported: N <= 32, R <= 4, D <= 64, D * H * W < 2^31 (else WM_EUNSUPPORTED: use wm_selscan_fwd); any H, W.
  *   W % 4 == 0 with 16-byte aligned x / y buffers: 16-byte tile accesses; otherwise (odd widths, fp32 planes only)
  *   the same kernels with element-wise tile accesses, slower per position.
- *   The workspace size depends on `merged` (three temporary y buffers).
+ *   The workspace size depends on `merged` (three temporary y buffers) and on wm_ss2d_core_carry_select.
  */
 size_t wm_ss2d_core_fwd_workspace_bytes(int B, int D, int H, int W, int N, int R, int merged);
+/*   wm_ss2d_core_carry_select  what the chunk-reduce launch of wm_ss2d_core_fwd leaves for the carry over chunks (host state, as
+ *   wm_conv2d_select): 0 (default) one sum of dt per (chunk, batch, channel), from which the carry launch forms
+ *   P = exp2(sum_dt * A); 1 the NP values of P themselves (the form until this selector existed: 16-32 times the words for the
+ *   same information).  The outputs have the same bits either way (parity tests and per-call A/B runs pin each in turn);
+ *   wm_ss2d_core_fwd_workspace_bytes answers for the current choice, so size the workspace after selecting.  Other values: WM_EINVAL.
+ */
+int wm_ss2d_core_carry_select(int mode);
 /*   Host-only: the work split wm_ss2d_core_fwd uses for this shape (no GPU needed; tests and tools).
  *   out[0..9] = waves per workgroup, rows per column segment, segments per column, column tiles, column workgroup slots
  *   per direction, steps per row chunk, row chunks, row workgroups per direction, workgroups per launch, estimated

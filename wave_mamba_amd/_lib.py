@@ -31,6 +31,7 @@ SIGNATURES = {
     "wm_selscan_bwd": (_i, [_p] * 15 + [_p, _sz] + [_i] * 6 + [_p]),
     "wm_ss2d_core_fwd_workspace_bytes": (_sz, [_i] * 7),
     "wm_ss2d_core_plan": (_i, [_i] * 6 + [_c.POINTER(_i)]),
+    "wm_ss2d_core_carry_select": (_i, [_i]),
     "wm_ss2d_core_fwd": (_i, [_p] * 10 + [_i, _p, _sz, _p] + [_i] * 7 + [_p]),
     "wm_ss2d_core_prep_bytes": (_sz, [_i]),
     "wm_ss2d_core_prep": (_i, [_p] * 6 + [_i] * 3 + [_p]),

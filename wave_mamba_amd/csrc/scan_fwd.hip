@@ -87,9 +87,15 @@ struct CorePlan {
     int row_chunk, row_nchunks, row_wgs, row_cpw;
     int col_seg, col_nseg, col_tiles, col_wgs;
     long long col_nchunks, max_chunks;
-    size_t half_bytes, ytmp_bytes, prep_bytes, total;   // one P (or H) array of one direction; merged-mode y buffers;
+    size_t half_bytes, ytmp_bytes, prep_bytes, total;   // one H (or stored-P) array of one direction; merged-mode y buffers;
                                                         // the prep kernel's output; everything
+    size_t p_bytes;                                     // what one direction keeps for P: a sum_dt array [chunk][B * D]
+                                                        // (half_bytes / NP), or half_bytes on the stored-P path
 };
+
+// 0: the reduce pass stores sum_dt and ss2d_core_carry_kernel forms P; 1: the reduce pass stores P, selscan_carry_kernel
+// (wm_ss2d_core_carry_select; the same H_in bits either way: tests/test_core_carry.py)
+static std::atomic<int> g_core_carry_select{0};
 
 // Length of one core launch (in row-tile times) under the dispatch model of core_plan's comment, replaying
 // ss2d_core_kernel's blockIdx -> (direction, slot) mapping.  Costs measured on MI355X (tools/bench_core.py with
@@ -151,7 +157,7 @@ static double core_makespan(const CorePlan& pl, int B, int H, double bound) {
     return span + kCarry * (double)chunks;
 }
 
-static int core_plan(CorePlan& pl, int B, int D, int H, int W, int N, int R, int merged) {
+static int core_plan(CorePlan& pl, int B, int D, int H, int W, int N, int R, int merged, bool stored_p) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || N <= 0 || R <= 0) return WM_EINVAL;
     if (N > 32 || R > 4 || D > 64) return WM_EUNSUPPORTED;
     const long long L = (long long)H * W;
@@ -243,7 +249,8 @@ static int core_plan(CorePlan& pl, int B, int D, int H, int W, int N, int R, int
     pl.half_bytes = up((size_t)pl.max_chunks * B * D * pl.NP * sizeof(float));
     pl.ytmp_bytes = merged ? up((size_t)B * D * L * sizeof(float)) : 0;
     pl.prep_bytes = up((size_t)4 * (pl.NP == 16 ? CoreCfg<16>::PREP : CoreCfg<32>::PREP) * sizeof(float));
-    pl.total = 8 * pl.half_bytes + 3 * pl.ytmp_bytes + pl.prep_bytes;
+    pl.p_bytes = stored_p ? pl.half_bytes : up((size_t)pl.max_chunks * B * D * sizeof(float));
+    pl.total = 4 * (pl.half_bytes + pl.p_bytes) + 3 * pl.ytmp_bytes + pl.prep_bytes;
     return WM_OK;
 }
 
@@ -280,15 +287,35 @@ static int core_launch(const CoreArgs& a, const CorePlan& pl, bool do_prep, hipS
             hipLaunchKernelGGL((ss2d_core_kernel<NP, NW, 1, RHI, TP, VEC>), grid, block, lds, st, a);
         }
         ProfScope ps(3, st);
-        CarryBatch cb{};
         const int order[4] = {0, 2, 1, 3};
-        for (int i = 0; i < 4; ++i) {
-            const int k = order[i];
-            cb.d[i] = CarryDir{a.wsP[k], a.wsH[k], nullptr, nullptr, (k & 1) ? (int)pl.col_nchunks : pl.row_nchunks, 0};
-        }
         const long long nchains = (long long)a.B * a.D * NP;
-        hipLaunchKernelGGL((selscan_carry_kernel<false>), dim3((unsigned)((nchains + 15) / 16), 1, 4), dim3(1024), 0,
-                           st, cb, nchains);
+        if (a.sdt[0]) {
+            CoreCarryBatch cb{};
+            for (int i = 0; i < 4; ++i) {
+                const int k = order[i];
+                cb.d[i] = CoreCarryDir{a.sdt[k], a.wsH[k], a.prep + (size_t)k * CoreCfg<NP>::PREP + CoreCfg<NP>::P_A2,
+                                       (k & 1) ? (int)pl.col_nchunks : pl.row_nchunks};
+            }
+            // summaries per segment of the longest direction -> how many a thread keeps in registers between fold and re-walk
+            // (the kernel's KEEP; 36 x 5 registers is what two waves per SIMD leave); longer sequences stream them twice
+            const int per = (int)((pl.max_chunks + kCarrySeg - 1) / kCarrySeg);
+#define WM_CARRY_GO(KEEP)                                                                                                      \
+    hipLaunchKernelGGL((ss2d_core_carry_kernel<NP, KEEP>), dim3((unsigned)((nchains + kCoreCarryChains - 1) / kCoreCarryChains), 1, 4), \
+                       dim3(512), 0, st, cb, a.B * a.D, a.D)
+            if (per <= 16) WM_CARRY_GO(16);
+            else if (per <= 24) WM_CARRY_GO(24);
+            else if (per <= 36) WM_CARRY_GO(36);
+            else WM_CARRY_GO(0);
+#undef WM_CARRY_GO
+        } else {
+            CarryBatch cb{};
+            for (int i = 0; i < 4; ++i) {
+                const int k = order[i];
+                cb.d[i] = CarryDir{a.wsP[k], a.wsH[k], nullptr, nullptr, (k & 1) ? (int)pl.col_nchunks : pl.row_nchunks, 0};
+            }
+            hipLaunchKernelGGL((selscan_carry_kernel<false>), dim3((unsigned)((nchains + 15) / 16), 1, 4), dim3(1024), 0,
+                               st, cb, nchains);
+        }
     }
     {
         ProfScope ps(8, st);
@@ -339,7 +366,7 @@ int wm_selscan_fwd(const float* u, const float* delta, const float* A, const flo
 size_t wm_ss2d_core_fwd_workspace_bytes(int B, int D, int H, int W, int N, int R, int merged) {
     // (sized for fp32 planes; bf16 planes need less for the merged mode's temporaries)
     CorePlan pl;
-    if (core_plan(pl, B, D, H, W, N, R, merged == 1) != WM_OK) return 0;
+    if (core_plan(pl, B, D, H, W, N, R, merged == 1, g_core_carry_select.load(std::memory_order_relaxed) == 1) != WM_OK) return 0;
     return pl.total;
 }
 
@@ -364,10 +391,16 @@ int wm_ss2d_core_prep(const float* x_proj_weight, const float* dt_projs_weight, 
     return launch_status();
 }
 
+int wm_ss2d_core_carry_select(int mode) {
+    if (mode < 0 || mode > 1) return WM_EINVAL;
+    g_core_carry_select.store(mode, std::memory_order_relaxed);
+    return WM_OK;
+}
+
 int wm_ss2d_core_plan(int B, int D, int H, int W, int N, int R, int* out10) {
     if (!out10) return WM_ENULL;
     CorePlan pl;
-    const int rc = core_plan(pl, B, D, H, W, N, R, 0);
+    const int rc = core_plan(pl, B, D, H, W, N, R, 0, false);
     if (rc) return rc;
     out10[0] = pl.NW; out10[1] = pl.col_seg; out10[2] = pl.col_nseg; out10[3] = pl.col_tiles; out10[4] = pl.col_wgs;
     out10[5] = pl.row_chunk; out10[6] = pl.row_nchunks; out10[7] = pl.row_wgs;      // (row_wgs x 2 NW chunks, taken on demand)
@@ -384,7 +417,8 @@ int wm_ss2d_core_fwd(const void* x, const float* x_proj_weight, const float* dt_
     if (B == 0 || D == 0 || H == 0 || W == 0) return (B < 0 || D < 0 || H < 0 || W < 0) ? WM_EINVAL : WM_OK;
     if (plane_dtype != WM_F32 && plane_dtype != WM_BF16) return WM_EUNSUPPORTED;
     CorePlan pl;
-    int rc = core_plan(pl, B, D, H, W, N, R, merged == 1);
+    const bool stored_p = g_core_carry_select.load(std::memory_order_relaxed) == 1;      // read once: sizes and launch agree
+    int rc = core_plan(pl, B, D, H, W, N, R, merged == 1, stored_p);
     if (rc) return rc;
     if (!x || !x_proj_weight || !dt_projs_weight || !dt_projs_bias || !A_logs || !Ds || !y_row_fwd) return WM_ENULL;
     if (merged < 0 || merged > 1) return WM_EINVAL;       // (2 was round 4's two-plane mode: measured slower, deleted in round 5)
@@ -406,11 +440,13 @@ int wm_ss2d_core_fwd(const void* x, const float* x_proj_weight, const float* dt_
     CoreArgs a;
     a.x = x; a.Wx = x_proj_weight; a.Wdt = dt_projs_weight; a.dtb = dt_projs_bias; a.A_logs = A_logs; a.Ds = Ds;
     char* w = (char*)workspace;
-    for (int k = 0; k < 4; ++k) {
-        a.wsP[k] = (float*)(w + (size_t)(2 * k) * pl.half_bytes);
-        a.wsH[k] = (float*)(w + (size_t)(2 * k + 1) * pl.half_bytes);
+    for (int k = 0; k < 4; ++k) {        // [H x 4 | P or sum_dt x 4 | merged-mode y x 3 | prep]
+        a.wsH[k] = (float*)(w + (size_t)k * pl.half_bytes);
+        float* pk = (float*)(w + 4 * pl.half_bytes + (size_t)k * pl.p_bytes);
+        a.wsP[k] = stored_p ? pk : nullptr;
+        a.sdt[k] = stored_p ? nullptr : pk;
     }
-    char* yt = w + 8 * pl.half_bytes;
+    char* yt = w + 4 * (pl.half_bytes + pl.p_bytes);
     a.prep = prepared ? (const float*)prepared : (const float*)(yt + 3 * pl.ytmp_bytes);
     if (prepared && !aligned16(prepared)) return WM_EALIGN;
     // direction k: 0 row forward, 1 column forward, 2 row reversed, 3 column reversed (the reference's xs order, :451-452)

@@ -354,9 +354,12 @@ __global__ __launch_bounds__(1024) void selscan_carry_kernel(CarryBatch cb, long
     const int per = (nchunks + kCarrySeg - 1) / kCarrySeg;
     const int c0 = min(nchunks, seg * per), c1 = min(nchunks, c0 + per);
     float P = 1.0f, H = 0.0f;
-    // per <= 16 (every sequence of <= 1024 summaries: the case this kernel is launched for): the thread's summaries stay in
-    // registers between the fold and the re-walk - read once instead of twice (the op is its traffic: 32 MB of summaries per
-    // call of the fused core at UHD level 1, 35 us with the second read)
+    // per <= 16 (every sequence of <= 1024 summaries: the case launch_carry_batch launches this kernel for): the thread's
+    // summaries stay in registers between the fold and the re-walk - read once instead of twice.  The op is its traffic.  The
+    // fused core's forward has about 2000 summaries per direction at UHD levels 1 and 2 (per = 34, both arrays read twice here:
+    // 53 us per launch) and 900-960 at level 3 (19 us); it now runs ss2d_core_carry_kernel (ss2d_core.hip.h), which reads
+    // sum_dt in place of P and keeps up to 36 summaries per thread (31 / 26 / 14 us at levels 1 / 2 / 3,
+    // profiles/core_carry/README.md), and reaches this kernel only under wm_ss2d_core_carry_select(1).
     const bool keep = per <= 16;                           // uniform
     float pk[16], hk[16];
     if (ok && keep) {

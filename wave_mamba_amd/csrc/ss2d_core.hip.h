@@ -25,7 +25,8 @@
 //     workgroup fetches [64 ch][16 rows][NW columns] with 4*NW-byte runs (one 64-B DRAM burst at NW = 16) and
 //     scatters the columns to the waves' tiles through LDS - no transposed copy of x or y ever exists, and the
 //     recurrence code is the row directions' code.
-//   * L-split: chunk-reduce (P = prod a, H = end state from 0) -> carry over chunks -> chunk-scan from H_in.  Every
+//   * L-split: chunk-reduce (P = prod a, H = end state from 0) -> carry over chunks -> chunk-scan from H_in.  P is a function
+//     of the chunk's sum of dt and of A: the reduce pass stores that one float per channel and the carry forms P.  Every
 //     exponential is evaluated twice (once per pass): with lane = channel and N states per lane there is nothing
 //     else to repeat.  Ragged tails are masked steps (dt := 0 => a = 1, b = 0: the state passes through).
 //   * y[k] goes to the direction's own (B, D, L) buffer in row-major positions; the consumer adds the four
@@ -85,6 +86,8 @@ struct CoreArgs {
     void* y[4];              // y of direction k, (B, D, L), row-major positions, fp32 or bf16
     float* wsP[4];           // chunk summaries of direction k: [chunk][b * D + d][NP]
     float* wsH[4];
+    float* sdt[4];           // sum of dt over the chunk, [chunk][b * D + d]: P = exp2(sum_dt * A) is formed by the carry
+                             // (ss2d_core_carry_kernel); NULL: the reduce pass stores P itself (wm_ss2d_core_carry_select(1))
     int B, D, H, W, L, N, R;
     int row_chunk, row_nchunks, row_wgs;        // steps per row chunk (multiple of 16), chunks, workgroups per direction
     int row_cpw;                                // row chunks per workgroup (handed to its waves on demand)
@@ -635,12 +638,20 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
 
     if (PHASE == 1 && active && live) {
 #pragma unroll
-        for (int q = 0; q < NP / 4; ++q) {
+        for (int q = 0; q < NP / 4; ++q)
             *reinterpret_cast<float4*>(p.wsH[k] + wsrow + 4 * q) =
                 make_float4(h[2 * q].x, h[2 * q].y, h[2 * q + 1].x, h[2 * q + 1].y);
-            const v2f p0 = exp2_2(splat(sum_dt) * WM_A2(2 * q));
-            const v2f p1 = exp2_2(splat(sum_dt) * WM_A2(2 * q + 1));
-            *reinterpret_cast<float4*>(p.wsP[k] + wsrow + 4 * q) = make_float4(p0.x, p0.y, p1.x, p1.y);
+        // P = exp2(sum_dt * A[n]) restates one float NP times: the chunk stores sum_dt (a 256-byte row at D = 64) and the
+        // carry forms P from it and the prep buffer's A with this same expression
+        if (p.sdt[k]) {
+            p.sdt[k][(chunk * p.B + b) * D + d] = sum_dt;
+        } else {
+#pragma unroll
+            for (int q = 0; q < NP / 4; ++q) {
+                const v2f p0 = exp2_2(splat(sum_dt) * WM_A2(2 * q));
+                const v2f p1 = exp2_2(splat(sum_dt) * WM_A2(2 * q + 1));
+                *reinterpret_cast<float4*>(p.wsP[k] + wsrow + 4 * q) = make_float4(p0.x, p0.y, p1.x, p1.y);
+            }
         }
     }
     if (!COL) core_lds_fence();                          // the wave's tiles are its own: nothing of this chunk is pending
@@ -648,6 +659,125 @@ __device__ __forceinline__ void core_body(const CoreArgs& p, const int k, const 
 }
 
 #undef WM_A2
+
+// Carry of the fused core's forward: H_in[c + 1] = P[c] * H_in[c] + H[c] over the chunks of each chain (b, d, n), all four
+// directions in one launch (blockIdx.z).  Same split and association order as selscan_carry_kernel<false> - kCarrySeg segments
+// of per = ceil(nchunks / kCarrySeg) chunks: fold each segment from (1, 0), combine the segment aggregates serially, re-walk
+// the segment replacing H[c] by its carry-in - so H_in has the same bits.  What differs is what moves:
+//   * P[c][chain] is not read: it is exp2(sum_dt[c][b, d] * A[d][n]), formed here from the reduce pass's sum_dt and the
+//     direction's prep buffer with the reduce pass's operands (the same fp32 product, rounded once, into the same v_exp_f32);
+//   * a lane owns FOUR consecutive states of one channel (one 16-byte access to H, one sum_dt for the four), 8 lanes along a
+//     chunk row and 8 segments per wave: a wave's load or store covers eight whole 128-byte lines.  A 512-thread block owns
+//     32 chains x 64 segments - 128 blocks at B D = 64, N <= 16.  Measured per launch at UHD levels 1 / 2 / 3 (us, per-class
+//     events, profiles/core_carry/variants.txt): 16 lanes per run (256-byte runs, 1024 threads, 64 blocks, registers for 16
+//     summaries only) 44.9 / 39.4 / 19.1; 4 lanes (64-byte runs, 256 blocks) 31.2 / 28.0 / 18.3; this form 31.7 / 26.4 / 14.4;
+//     stored P with selscan_carry_kernel 52.7 / 54.0 / 19.2.
+// KEEP > 0 (per <= KEEP, the host's choice): sum_dt and H stay in registers between fold and re-walk (P is recomputed: 4
+// v_exp_f32 per summary quad) - H is read once; KEEP == 0 streams both twice, eight summaries at a time.
+constexpr int kCoreCarryLpr = 8, kCoreCarryChains = 4 * kCoreCarryLpr;
+struct CoreCarryDir { const float* sdt; float* wsH; const float* A2; int nchunks; };      // A2: prep + CoreCfg::P_A2 of the direction
+struct CoreCarryBatch { CoreCarryDir d[4]; };
+
+template <int NP, int KEEP>
+__global__ __launch_bounds__(64 * kCoreCarryLpr) void ss2d_core_carry_kernel(CoreCarryBatch cb, int nbd, int D) {      // nbd = B * D
+    const CoreCarryDir cd = cb.d[blockIdx.z];
+    const float* __restrict__ sdt = cd.sdt;
+    float* __restrict__ wsH = cd.wsH;
+    const int nchunks = cd.nchunks;
+    const long long nchains = (long long)nbd * NP;
+    constexpr int LPR = kCoreCarryLpr;
+    __shared__ float4 sP[kCarrySeg][LPR];
+    __shared__ float4 sH[kCarrySeg][LPR];
+    const int cq = threadIdx.x % LPR;                      // chain quad within the block
+    const int seg = threadIdx.x / LPR;                     // 0..63
+    const long long chain = (long long)blockIdx.x * (4 * LPR) + 4 * cq;      // first of the lane's four chains (nchains % 16 == 0)
+    const bool ok = chain < nchains;
+    const int bd = ok ? (int)(chain / NP) : 0, n0 = (int)(chain % NP), d = bd % D;
+    const v2f A2a = *reinterpret_cast<const v2f*>(cd.A2 + ((n0 / 2) * 64 + d) * 2);          // states n0, n0 + 1
+    const v2f A2b = *reinterpret_cast<const v2f*>(cd.A2 + ((n0 / 2 + 1) * 64 + d) * 2);      // states n0 + 2, n0 + 3
+    const int per = (nchunks + kCarrySeg - 1) / kCarrySeg;
+    const int c0 = min(nchunks, seg * per), c1 = min(nchunks, c0 + per);
+    float4 P = make_float4(1.f, 1.f, 1.f, 1.f), H = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto pof = [&](bool in, float s) {                     // a chunk's P quad; past the segment's end the identity (1, 0)
+        // Plain fp32 products: each rounds as its half of the reduce pass's packed multiply does.  Written as
+        // exp2_2(splat(s) * A2a) this was `v_pk_mul_f32 v, v, v op_sel_hi:[1,0]` (a (low, low) broadcast of a VGPR), and with the
+        // side streams' matrix-core convolutions on the chip 2-4 of 20 multi-stream UHD forwards came out 2e-6 .. 1e-5 off the
+        // single-stream order, every time (tests/test_gpu_parity.py::test_multi_stream_uhd_bit_equal; the parent, the stored-P
+        // selector and this form: none) - one more packed form that is not safe beside LDS-fed MFMAs (wave_mamba_amd/
+        // _lint_packed_f32.py lists the others; that lint does not refuse this one, the scan kernels carry it).
+        const float p0 = __builtin_amdgcn_exp2f(s * A2a.x), p1 = __builtin_amdgcn_exp2f(s * A2a.y);
+        const float p2 = __builtin_amdgcn_exp2f(s * A2b.x), p3 = __builtin_amdgcn_exp2f(s * A2b.y);
+        return make_float4(in ? p0 : 1.0f, in ? p1 : 1.0f, in ? p2 : 1.0f, in ? p3 : 1.0f);
+    };
+    auto step = [](float4& c, const float4& p, const float4& hc) {
+        c.x = fmaf(p.x, c.x, hc.x); c.y = fmaf(p.y, c.y, hc.y); c.z = fmaf(p.z, c.z, hc.z); c.w = fmaf(p.w, c.w, hc.w);
+    };
+    auto fold = [&](const float4& p, const float4& hc) {
+        step(H, p, hc);
+        P.x *= p.x; P.y *= p.y; P.z *= p.z; P.w *= p.w;
+    };
+    auto load = [&](int c, bool in, float& s, float4& hc) {      // unconditional loads from clamped indices, masked after
+        const long long cc = in ? c : 0;
+        s = sdt[cc * nbd + bd];
+        const float4 v = *reinterpret_cast<const float4*>(wsH + cc * nchains + chain);
+        hc = make_float4(in ? v.x : 0.f, in ? v.y : 0.f, in ? v.z : 0.f, in ? v.w : 0.f);
+    };
+    auto put = [&](int c, const float4& v) { *reinterpret_cast<float4*>(wsH + (long long)c * nchains + chain) = v; };
+    constexpr int KB = KEEP ? KEEP : 8;
+    float sk[KB]; float4 hk[KB];
+    if (ok) {
+        if constexpr (KEEP > 0) {
+#pragma unroll
+            for (int j = 0; j < KB; ++j) load(c0 + j, c0 + j < c1, sk[j], hk[j]);
+#pragma unroll
+            for (int j = 0; j < KB; ++j) fold(pof(c0 + j < c1, sk[j]), hk[j]);
+        } else {
+            for (int c = c0; c < c1; c += KB) {
+#pragma unroll
+                for (int j = 0; j < KB; ++j) load(c + j, c + j < c1, sk[j], hk[j]);
+#pragma unroll
+                for (int j = 0; j < KB; ++j) fold(pof(c + j < c1, sk[j]), hk[j]);
+            }
+        }
+    }
+    sP[seg][cq] = P; sH[seg][cq] = H;
+    __syncthreads();
+    // serial combine over the earlier segments, aggregates read eight at a time (the wave's trip count is its last segment's)
+    float4 carry = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int send = __builtin_amdgcn_readfirstlane((int)(threadIdx.x | 63) / LPR);
+    constexpr int CB = KEEP > 24 ? 2 : 8;                  // (the kept summaries leave that many registers)
+    for (int s0 = 0; s0 < send; s0 += CB) {
+        float4 p8[CB], h8[CB];
+#pragma unroll
+        for (int j = 0; j < CB; ++j) { p8[j] = sP[s0 + j][cq]; h8[j] = sH[s0 + j][cq]; }
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            float4 nx = carry;
+            step(nx, p8[j], h8[j]);
+            const bool take = s0 + j < seg;
+            carry = make_float4(take ? nx.x : carry.x, take ? nx.y : carry.y, take ? nx.z : carry.z, take ? nx.w : carry.w);
+        }
+    }
+    if (ok) {
+        if constexpr (KEEP > 0) {
+#pragma unroll
+            for (int j = 0; j < KB; ++j) {
+                if (c0 + j < c1) put(c0 + j, carry);
+                step(carry, pof(c0 + j < c1, sk[j]), hk[j]);
+            }
+        } else {
+            for (int c = c0; c < c1; c += KB) {
+#pragma unroll
+                for (int j = 0; j < KB; ++j) load(c + j, c + j < c1, sk[j], hk[j]);
+#pragma unroll
+                for (int j = 0; j < KB; ++j) {
+                    if (c + j < c1) put(c + j, carry);
+                    step(carry, pof(c + j < c1, sk[j]), hk[j]);
+                }
+            }
+        }
+    }
+}
 
 // Workgroup -> (batch, direction, slot).  Per batch: 2 * col_wgs column slots first (k = 1 / 3 interleaved), then
 // 2 * row_wgs row slots (k = 0 / 2 interleaved): the column workgroups are the long ones (a whole column segment, three
