@@ -101,6 +101,79 @@ def test_deterministic_forms_and_gathers_validate_before_launch():
     assert lib.wm_channel_gather_fwd(N, N, N, 0, 2, 5, 4, N) == 0 and lib.wm_channel_gather_bwd(N, N, N, 1, 2, 5, 0, N) == 0
 
 
+def test_conv2d_entries_and_core_return_codes_in_order():
+    """Every entry over Conv2dArgs, and wm_ss2d_core_fwd, by host arithmetic alone (all pointers NULL): the code for each refusal and
+    the order in which the refusals are reached - a bad dimension, then the entry's unsupported form, then an empty problem (WM_OK),
+    then a NULL tensor.  The order is observable: a case that fails two checks answers with the earlier one."""
+    lib = _lib.load()
+    N, OK, EINVAL, ENULL, EUNSUP = None, _lib.WM_OK, _lib.WM_EINVAL, _lib.WM_ENULL, _lib.WM_EUNSUPPORTED
+
+    def conv(B=1, Ca=32, Cb=0, Cb_src=0, Cout=32, H=8, W=8, ks=3):
+        return lib.wm_conv2d_fwd(*[N] * 8, B, Ca, Cb, Cb_src, Cout, H, W, ks, N)
+    assert conv(B=-1) == EINVAL and conv(Cb=-1) == EINVAL and conv(Cb_src=-1) == EINVAL and conv(Ca=0) == EINVAL and conv(Ca=-4) == EINVAL
+    assert conv(Cout=0) == EINVAL and conv(H=-1) == EINVAL and conv(W=-1) == EINVAL
+    assert conv(B=-1, ks=5) == EINVAL                                      # a bad dimension precedes the unsupported form
+    assert conv(ks=5) == EUNSUP and conv(ks=0) == EUNSUP and conv(ks=2) == EUNSUP
+    assert conv(ks=5, B=0) == EUNSUP                                       # ... which precedes the empty check
+    assert conv(B=0) == OK and conv(H=0) == OK and conv(W=0) == OK and conv(B=0, ks=1) == OK
+    assert conv(B=0, Cb=16) == OK                                          # ... which precedes the NULL check
+    assert conv() == ENULL and conv(ks=1) == ENULL
+    assert conv(Cb=16, Cb_src=16) == ENULL                                 # Cb > 0 with a NULL xb
+    assert conv(Ca=36, Cb=16, Cb_src=16) == ENULL                          # (before the Ca % 8 rule of the second source)
+    assert conv(B=65536) == ENULL and conv(H=1 << 16, W=1 << 15) == ENULL  # (before the size limits)
+
+    def ln(B=1, Cin=32, Cout=32, H=8, W=8):
+        return lib.wm_conv2d_ln_fwd(N, N, N, 1e-6, N, N, N, N, B, Cin, Cout, H, W, N)
+    assert ln(B=-1) == EINVAL and ln(Cin=0) == EINVAL and ln(Cout=0) == EINVAL and ln(H=-1) == EINVAL and ln(W=-1) == EINVAL
+    assert ln(B=-1, Cin=16) == EINVAL
+    assert ln(Cin=16) == EUNSUP and ln(Cin=64) == EUNSUP and ln(Cin=16, B=0) == EUNSUP
+    assert ln(B=0) == OK and ln(H=0) == OK and ln(W=0) == OK
+    assert ln() == ENULL and ln(Cout=96) == ENULL and ln(B=65536) == ENULL
+
+    def f16(B=1, Cin=32, Cout=32, H=8, W=8, ks=3, dgrad=0):
+        return lib.wm_conv2d_f16_steps(*[N] * 6, B, Cin, Cout, H, W, ks, dgrad, N)
+    assert f16(H=-1) == EINVAL and f16(B=-1) == EINVAL and f16(Cin=0) == EINVAL and f16(Cout=0) == EINVAL and f16(W=-1) == EINVAL
+    assert f16(H=-1, ks=5) == EINVAL
+    assert f16(ks=5) == EUNSUP and f16(ks=5, B=0) == EUNSUP
+    assert f16(B=0) == OK and f16(H=0) == OK and f16(W=0) == OK and f16(B=0, ks=1) == OK
+    assert f16() == ENULL and f16(ks=1) == ENULL and f16(dgrad=1) == ENULL
+
+    def cdwt(B=1, Cin=3, Cout=32, H=8, W=8, dtype=_lib.WM_F32):
+        return lib.wm_conv2d_dwt_fwd(*[N] * 7, B, Cin, Cout, H, W, dtype, N)
+    assert cdwt(B=-1) == EINVAL and cdwt(Cin=0) == EINVAL and cdwt(Cout=0) == EINVAL
+    assert cdwt(H=7) == EINVAL and cdwt(W=7) == EINVAL
+    assert cdwt(H=7, Cout=64) == EINVAL and cdwt(H=7, dtype=_lib.WM_BF16) == EINVAL   # an odd side precedes the unsupported form
+    assert cdwt(Cout=64) == EUNSUP and cdwt(dtype=_lib.WM_BF16) == EUNSUP
+    assert cdwt(Cout=64, B=0) == EUNSUP
+    assert cdwt(B=0) == OK and cdwt(H=0) == OK and cdwt(W=0) == OK
+    assert cdwt() == ENULL and cdwt(Cin=32) == ENULL and cdwt(B=65536) == ENULL
+
+    def idwtc(B=1, Cin=32, Cout=32, H=8, W=8, dtype=_lib.WM_F32):
+        return lib.wm_idwt_conv2d_fwd(*[N] * 6, B, Cin, Cout, H, W, dtype, N)
+    assert idwtc(B=-1) == EINVAL and idwtc(Cin=0) == EINVAL and idwtc(Cout=0) == EINVAL
+    assert idwtc(W=7) == EINVAL and idwtc(H=7) == EINVAL and idwtc(W=7, Cin=16) == EINVAL
+    assert idwtc(Cin=16) == EUNSUP and idwtc(dtype=_lib.WM_BF16) == EUNSUP and idwtc(Cin=16, B=0) == EUNSUP
+    assert idwtc(B=0) == OK and idwtc(H=0) == OK and idwtc(W=0) == OK
+    assert idwtc() == ENULL and idwtc(Cout=3) == ENULL and idwtc(B=65536) == ENULL
+
+    def gated(B=1, Ca=32, Cb=0, Cb_src=0, Cout=32, H=8, W=8):
+        return lib.wm_conv2d_gated_fwd(*[N] * 7, B, Ca, Cb, Cb_src, Cout, H, W, N)
+    assert gated(Cout=0) == EINVAL and gated(B=-1) == EINVAL and gated(Ca=0) == EINVAL and gated(Cb=-1) == EINVAL
+    assert gated(Cb_src=-1) == EINVAL and gated(H=-1) == EINVAL and gated(W=-1) == EINVAL
+    assert gated(Cout=0, B=0) == EINVAL
+    assert gated(B=0) == OK and gated(H=0) == OK and gated(W=0) == OK and gated(B=0, Cb=16) == OK
+    assert gated() == ENULL and gated(Cout=64) == ENULL
+    assert gated(Cb=16, Cb_src=16) == ENULL and gated(Ca=36, Cb=16, Cb_src=16) == ENULL and gated(B=65536) == ENULL
+
+    # the SS2D core's launch: an empty problem answers first here, then the plane dtype and the plan's limits, then the NULLs
+    def core(B=1, D=64, H=8, W=8, n=16, R=2, dtype=_lib.WM_F32, merged=1):
+        return lib.wm_ss2d_core_fwd(*[N] * 10, merged, N, 0, N, B, D, H, W, n, R, dtype, N)
+    assert core(n=33) == EUNSUP and core(n=64) == EUNSUP and core(dtype=2) == EUNSUP
+    assert core(B=0) == OK and core(H=0) == OK and core(B=0, n=33) == OK
+    assert core(B=0, H=-1) == EINVAL
+    assert core() == ENULL and core(n=32) == ENULL and core(merged=0) == ENULL and core(dtype=_lib.WM_BF16) == ENULL
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/libwavemamba_hip.so")

@@ -30,10 +30,11 @@ that kernel's existing test (tests/test_gpu_parity.py), and to the project's bit
        (1, 32, 96, 96)    9216 / 4 = 2304 -> bpp 2 (cap 128); H W % 4 == 0: 16-byte form
        (2, 16, 91, 91)    8281 % 4 == 1: element-wise; floor(8281 / 4) = 2070 -> bpp 2
        (1, 64, 192, 256)  49152 / 4 = 12288 -> bpp 6 (cap 64)
- 7 wm_conv2d_fwd, more than three 32-channel row tiles   conv.hip:154-177: mtot = ceil(Cout / 32); 1x1: MT = 3 while >= 3 tiles are
+ 7 wm_conv2d_fwd, more than three 32-channel row tiles   conv.hip, conv2d_walk: mtot = ceil(Cout / 32); 1x1: MT = 3 while >= 3 tiles are
      left, then 2 or 1; 3x3: MT = 2 while >= 2 are left, then 1 (with a residual the wave-specialised kernel goes one tile a launch)
        Cout 128: mtot 4 -> 1x1 3 + 1 (mbase 3), 3x3 2 + 2 (mbase 2);  Cout 160: mtot 5 -> 1x1 3 + 2, 3x3 2 + 2 + 1;
        Cout 136: mtot 5, the last tile holds 8 channels
+     and the check every entry over Conv2dArgs ends with (conv_tail_check): B = 65536 > gridDim.y on a 2 x 2 map, real operands
  8 wm_layernorm2d_bwd, the 512-workgroup clamp   lfss.hip:411-415: min(512, ceil(B H W tpp / 256)), tpp = 2 for C >= 32 (pair kernel)
        (2, 32, 192, 192) 73728 x 2 / 256 = 576;  (2, 64, 160, 208) 66560 x 2 / 256 = 520;  (2, 16, 257, 257) ceil(132098 / 256) = 517
  9 wm_layernorm_tok_bwd / _fwd clamps   lfss.hip:416-420, 479-481: tokens per workgroup tpb = 256 / (C / 4); backward min(1024, ceil(T / tpb)),
@@ -310,7 +311,7 @@ def conv3x3_impl(request):
 def test_conv2d_more_than_three_row_tiles(conv3x3_impl, ks, B, Ca, Cb, Cout, H, W, bias, res):
     """test_conv2d_vs_torch past 96 output channels: a second launch at mbase = 3 (1x1) / mbase = 2 (3x3, both kernels), a last row
     tile of 8 channels, and the epilogue's residual read at mbase > 0."""
-    assert (Cout + 31) // 32 > 3                                                  # conv.hip:152-177
+    assert (Cout + 31) // 32 > 3                                                  # conv.hip, conv2d_walk
     gg = gen(Ca * 100 + Cout + H + ks)
     xa = torch.randn(B, Ca, H, W, generator=gg)
     xb = torch.randn(B, Cb, H, W, generator=gg) if Cb else None
@@ -323,6 +324,26 @@ def test_conv2d_more_than_three_row_tiles(conv3x3_impl, ks, B, Ca, Cb, Cout, H, 
         ref = ref + r.double()
     got = wm.ops.conv2d(*cu(xa, w, b, xb), residual=None if r is None else r.to(DEV))
     assert_close(got, ref.float(), 2e-5, f"conv2d ks={ks} {(B, Ca, Cb, Cout, H, W)} residual={res}")
+
+
+def test_conv2d_entries_refuse_a_batch_past_grid_y():
+    """Every entry over Conv2dArgs ends its checks with the same pair (conv.hip, conv_tail_check): B = 65536 on a 2 x 2 map is
+    WM_EUNSUPPORTED from each of them.  Every operand is a real tensor of the size the call describes, so an entry that lost the
+    check would compute or be refused by the runtime - it could not fault."""
+    B, C = 65536, 32
+    z = lambda *shape: torch.zeros(shape, device=DEV)
+    frag = lambda ks: torch.zeros(_lib.load().wm_conv2d_wfrag_bytes(C, C, ks), dtype=torch.uint8, device=DEV)
+    x, y, vec = z(B, C, 2, 2), z(B, C, 2, 2), z(C)
+    go = lambda name, *args: wm.ops._launch(x.device, name, *args, status=True)
+    for ks in (1, 3):
+        assert go("wm_conv2d_fwd", x, None, None, frag(ks), vec, None, None, y, B, C, 0, 0, C, 2, 2, ks) == _lib.WM_EUNSUPPORTED, ks
+        assert go("wm_conv2d_f16_steps", x, z(C, C, ks, ks), vec, y, z(2), frag(ks), B, C, C, 2, 2, ks, 0) == _lib.WM_EUNSUPPORTED, ks
+    assert go("wm_conv2d_ln_fwd", x, vec, vec, 1e-6, frag(1), vec, None, y, B, C, C, 2, 2) == _lib.WM_EUNSUPPORTED
+    assert go("wm_conv2d_gated_fwd", x, None, None, frag(3), frag(1), vec, y, B, C, 0, 0, C, 2, 2) == _lib.WM_EUNSUPPORTED
+    bands = [z(B, C, 1, 1) for _ in range(4)]
+    assert go("wm_conv2d_dwt_fwd", x, frag(3), vec, *bands, B, C, C, 2, 2, _lib.WM_F32) == _lib.WM_EUNSUPPORTED
+    assert go("wm_idwt_conv2d_fwd", bands[0], z(B, 3 * C, 1, 1), frag(3), vec, None, y, B, C, C, 2, 2, _lib.WM_F32) == _lib.WM_EUNSUPPORTED
+    torch.cuda.synchronize()                  # (wm_conv2d_f16_steps takes the operands' magnitudes before it reaches the check)
 
 
 # ------------------------------------------------------------------------------------------------

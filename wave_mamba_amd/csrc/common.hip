@@ -83,6 +83,19 @@ int lds_optin(const void* fn, int bytes, bool (&flags)[64]) {
     return WM_OK;
 }
 
+int device_cus(int* ncu) {
+    static std::atomic<int> cached[64];                          // 0: not asked yet (two threads may both ask: same answer)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return WM_EHIP;
+    int n = cached[dev].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return WM_EHIP;
+        cached[dev].store(n, std::memory_order_relaxed);
+    }
+    *ncu = n;
+    return WM_OK;
+}
+
 }  // namespace wm
 
 using namespace wm;

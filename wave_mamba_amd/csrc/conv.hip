@@ -9,6 +9,24 @@
 
 using namespace wm;
 
+// The operands every entry over Conv2dArgs has; what is particular to an entry (a second source, epilogue operands, LayerNorm
+// parameters, ...) it states itself, and everything it does not state keeps the struct's default (null / 0).
+static Conv2dArgs conv_args(const void* xa, int Ca, const void* wfrag, const float* bias, void* y, int Cout, int H, int W) {
+    Conv2dArgs a;
+    a.xa = (const float*)xa; a.wfrag = (const uint4*)wfrag; a.bias = bias; a.y = (float*)y;
+    a.Ca = Ca; a.Cout = Cout; a.H = H; a.W = W;
+    a.nch = (Ca + 15) / 16; a.mtot = (Cout + 31) / 32;
+    return a;
+}
+
+// The last two checks of every entry over Conv2dArgs: the batch is a grid dimension and pixel offsets are 32-bit; the kernels load
+// the fragments 16 bytes at a time.
+static int conv_tail_check(int B, int H, int W, const void* wfrag) {
+    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
+    if (!aligned16(wfrag)) return WM_EALIGN;
+    return WM_OK;
+}
+
 template <int KS, int RW, int MT, bool G1X1 = false, bool F16 = false, bool LNIN = false>
 static int conv2d_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
     constexpr int PAD = KS / 2;
@@ -43,8 +61,15 @@ static int conv2d_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
 #ifndef WM_CONV_WS_NPW1
 #define WM_CONV_WS_NPW1 4              // producer waves of the one-row-tile launches
 #endif
+#ifndef WM_CONV_RW1
+#define WM_CONV_RW1 3                  // first-generation 3x3, one row tile: 4 RW rows per tile (conv2d_walk)
+#endif
 static std::atomic<int> g_conv_select{0};
 static int conv_select_mode() { return g_conv_select.load(std::memory_order_relaxed); }
+// 64 x th tiles of a wave-specialised launch over the whole batch
+static long long conv_ws_ntiles(const wm::Conv2dArgs& a, int B, int th) {
+    return (long long)B * ((a.W + wm::kWsTW - 1) / wm::kWsTW) * ((a.H + th - 1) / th);
+}
 // th: tile rows of the launch that would run (2 x row tiles per workgroup)
 static bool conv_ws_enabled(const wm::Conv2dArgs& a, int B, int th) {
     const int mode = conv_select_mode();
@@ -55,33 +80,53 @@ static bool conv_ws_enabled(const wm::Conv2dArgs& a, int B, int th) {
     if (a.gate && a.res) return false;
     if (mode == 2) return true;
     if ((a.gate || a.res) && a.mtot > 1) return false;
-    const long long ntiles = (long long)B * ((a.W + wm::kWsTW - 1) / wm::kWsTW) * ((a.H + th - 1) / th);
-    return ntiles >= 768;
+    return conv_ws_ntiles(a, B, th) >= 768;
 }
 
 template <int RW, int MT, bool G1X1 = false, bool EPI = false, int NPW = 4, bool F16 = false, bool DWTE = false, bool IWTI = false>
 static int conv2d_ws_launch(const wm::Conv2dArgs& a, int B, hipStream_t st) {
     using Cfg = wm::ConvWsCfg<RW, MT, G1X1, NPW>;
     static bool configured[64] = {};
-    static int ncu[64] = {};
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return WM_EHIP;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (!configured[dev]) {
-            if (hipFuncSetAttribute((const void*)wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16, DWTE, IWTI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Cfg::LDS_BYTES) != hipSuccess) return WM_EHIP;
-            if (hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return WM_EHIP;
-            configured[dev] = true;
-        }
-    }
-    const long long ntiles = (long long)B * ((a.W + wm::kWsTW - 1) / wm::kWsTW) * ((a.H + Cfg::TH - 1) / Cfg::TH);
+    int ncu = 0;
+    int rc = wm::lds_optin((const void*)wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16, DWTE, IWTI>, Cfg::LDS_BYTES, configured);
+    if (!rc) rc = wm::device_cus(&ncu);
+    if (rc) return rc;
+    const long long ntiles = conv_ws_ntiles(a, B, Cfg::TH);
     if (ntiles >= (1ll << 31)) return WM_EUNSUPPORTED;
-    const int cus = std::max(8, ncu[dev] & ~7);
+    const int cus = std::max(8, ncu & ~7);
     const int G = (int)std::min<long long>(cus, ((ntiles + 7) / 8) * 8);
     hipLaunchKernelGGL((wm::conv3x3_ws_kernel<RW, MT, G1X1, EPI, NPW, F16, DWTE, IWTI>), dim3((unsigned)G), dim3(256 + 64 * NPW), Cfg::LDS_BYTES, st, a, B);
     return launch_status();
+}
+
+// The walk over the 32-channel row tiles of a dense convolution, ks in {1, 3}: which kernel takes how many tiles per launch.
+// F16: the training form (no epilogue operand, so its EPI kernel does not exist); LNIN: LayerNorm2d inside the staging (1x1 only).
+template <bool F16, bool LNIN>
+static int conv2d_walk(wm::Conv2dArgs& a, int B, int ks, hipStream_t st) {
+    for (int mb = 0, n; mb < a.mtot; mb += n) {
+        a.mbase = mb;
+        const int left = a.mtot - mb;
+        int rc = WM_EUNSUPPORTED;                            // (every branch below launches)
+        n = 1;                                               // row tiles this launch takes
+        if (LNIN || ks == 1) {
+            // 1x1 is bandwidth-bound: never read the input twice (3 row tiles in one launch on an 8-row tile)
+            if (left >= 3) { rc = conv2d_launch<1, 2, 3, false, F16, LNIN>(a, B, st); n = 3; }
+            else if (left == 2) { rc = conv2d_launch<1, 4, 2, false, F16, LNIN>(a, B, st); n = 2; }
+            else rc = conv2d_launch<1, 4, 1, false, F16, LNIN>(a, B, st);
+        } else if constexpr (!LNIN) {
+            // first generation, 32 output channels: 12-row tiles (49 KB of LDS: three workgroups per compute unit, staging slots
+            // 93 % used) beat 16-row tiles (two workgroups, 80 %) by 4-13 %; 64 channels keep 16 rows (two accumulator sets)
+            if (conv_ws_enabled(a, B, 8)) {
+                const bool epi = !F16 && (a.gate || a.res);
+                if (epi) { if constexpr (!F16) rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, true>(a, B, st); }
+                else if (left >= 2) { rc = conv2d_ws_launch<WM_CONV_WS_RW2, 2, false, false, 4, F16>(a, B, st); n = 2; }
+                else rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1, F16>(a, B, st);
+            } else if (left >= 2) { rc = conv2d_launch<3, 4, 2, false, F16>(a, B, st); n = 2; }
+            else rc = conv2d_launch<3, WM_CONV_RW1, 1, false, F16>(a, B, st);
+        }
+        if (rc) return rc;
+    }
+    return WM_OK;
 }
 
 extern "C" {
@@ -142,40 +187,14 @@ int wm_conv2d_fwd(const float* xa, const float* xb, const int* xb_index, const v
     if (!xa || !wfrag || !y || (Cb > 0 && !xb)) return WM_ENULL;
     if (Cb > 0 && Ca % 8 != 0) return WM_EUNSUPPORTED;   // an 8-channel fragment never straddles the two sources
     if (Cb > 0 && !xb_index && Cb_src != Cb) return WM_EINVAL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = xa; a.xb = Cb > 0 ? xb : nullptr; a.xb_idx = Cb > 0 ? xb_index : nullptr; a.wfrag = (const uint4*)wfrag;
-    a.bias = bias; a.gate = gate; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
-    a.Ca = Ca; a.Cb = Cb; a.Cbsrc = Cb_src; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = (Ca + Cb + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    Conv2dArgs a = conv_args(xa, Ca, wfrag, bias, y, Cout, H, W);
+    if (Cb > 0) { a.xb = xb; a.xb_idx = xb_index; }
+    a.Cb = Cb; a.Cbsrc = Cb_src; a.nch = (Ca + Cb + 15) / 16;
+    a.gate = gate; a.res = residual;
     ProfScope ps(ks == 3 ? 13 : 14, st);
-    for (int mb = 0; mb < a.mtot;) {
-        a.mbase = mb;
-        const int left = a.mtot - mb;
-        int rc;
-        if (ks == 3) {
-#ifndef WM_CONV_RW1
-#define WM_CONV_RW1 3
-#endif
-            // 32 output channels: 12-row tiles (49 KB of LDS: three workgroups per compute unit, staging slots 93 % used)
-            // beat 16-row tiles (two workgroups, 80 %) by 4-13 %; 64 channels keep 16 rows (two accumulator sets)
-            if (conv_ws_enabled(a, B, 8)) {
-                if (gate || residual) { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, true>(a, B, st); mb += 1; }
-                else if (left >= 2) { rc = conv2d_ws_launch<WM_CONV_WS_RW2, 2>(a, B, st); mb += 2; }
-                else { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1>(a, B, st); mb += 1; }
-            } else if (left >= 2) { rc = conv2d_launch<3, 4, 2>(a, B, st); mb += 2; }
-            else { rc = conv2d_launch<3, WM_CONV_RW1, 1>(a, B, st); mb += 1; }
-        } else {
-            // 1x1 is bandwidth-bound: never read the input twice (3 row tiles in one launch on an 8-row tile)
-            if (left >= 3) { rc = conv2d_launch<1, 2, 3>(a, B, st); mb += 3; }
-            else if (left == 2) { rc = conv2d_launch<1, 4, 2>(a, B, st); mb += 2; }
-            else { rc = conv2d_launch<1, 4, 1>(a, B, st); mb += 1; }
-        }
-        if (rc) return rc;
-    }
-    return WM_OK;
+    return conv2d_walk<false, false>(a, B, ks, st);
 }
 
 // y = conv1x1(LayerNorm2d(x)) + bias (+ residual): the LayerNorm of a 32-channel map inside the 1x1 kernel's staging (conv2d.hip.h, LNIN).
@@ -185,25 +204,13 @@ int wm_conv2d_ln_fwd(const float* x, const float* ln_weight, const float* ln_bia
     if (Cin != 32) return WM_EUNSUPPORTED;                 // callers run wm_layernorm2d_fwd + wm_conv2d_fwd
     if (B == 0 || H == 0 || W == 0) return WM_OK;
     if (!x || !ln_weight || !ln_bias || !wfrag || !y) return WM_ENULL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = x; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
-    a.bias = bias; a.gate = nullptr; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
-    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = 2; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = ln_weight; a.ln_b = ln_bias; a.ln_eps = ln_eps;
+    Conv2dArgs a = conv_args(x, Cin, wfrag, bias, y, Cout, H, W);
+    a.res = residual;
+    a.ln_w = ln_weight; a.ln_b = ln_bias; a.ln_eps = ln_eps;
     ProfScope ps(14, st);
-    for (int mb = 0; mb < a.mtot;) {
-        a.mbase = mb;
-        const int left = a.mtot - mb;
-        int rc;
-        if (left >= 3) { rc = conv2d_launch<1, 2, 3, false, false, true>(a, B, st); mb += 3; }
-        else if (left == 2) { rc = conv2d_launch<1, 4, 2, false, false, true>(a, B, st); mb += 2; }
-        else { rc = conv2d_launch<1, 4, 1, false, false, true>(a, B, st); mb += 1; }
-        if (rc) return rc;
-    }
-    return WM_OK;
+    return conv2d_walk<false, true>(a, B, 1, st);
 }
 
 // y = conv1x1(act(dwconv3x3(x) + dw_bias)) + bias (+ residual) in one kernel (dw_pw.hip.h): bit-identical to wm_dwconv3x3_fwd +
@@ -286,33 +293,12 @@ static int conv2d_fwd_f16(const float* x, const void* wfrag, const float* amax, 
     if (ks != 1 && ks != 3) return WM_EUNSUPPORTED;
     if (B == 0 || H == 0 || W == 0) return WM_OK;
     if (!x || !wfrag || !y || !amax) return WM_ENULL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = x; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
-    a.bias = bias; a.gate = nullptr; a.res = nullptr; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
-    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = (Cin + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = amax; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    Conv2dArgs a = conv_args(x, Cin, wfrag, bias, y, Cout, H, W);
+    a.amax = amax;
     ProfScope ps(ks == 3 ? 13 : 14, st);
-    for (int mb = 0; mb < a.mtot;) {
-        a.mbase = mb;
-        const int left = a.mtot - mb;
-        int rc;
-        if (ks == 3) {
-            if (conv_ws_enabled(a, B, 8)) {
-                if (left >= 2) { rc = conv2d_ws_launch<WM_CONV_WS_RW2, 2, false, false, 4, true>(a, B, st); mb += 2; }
-                else { rc = conv2d_ws_launch<WM_CONV_WS_RW1, 1, false, false, WM_CONV_WS_NPW1, true>(a, B, st); mb += 1; }
-            } else if (left >= 2) { rc = conv2d_launch<3, 4, 2, false, true>(a, B, st); mb += 2; }
-            else { rc = conv2d_launch<3, WM_CONV_RW1, 1, false, true>(a, B, st); mb += 1; }
-        } else {
-            if (left >= 3) { rc = conv2d_launch<1, 2, 3, false, true>(a, B, st); mb += 3; }
-            else if (left == 2) { rc = conv2d_launch<1, 4, 2, false, true>(a, B, st); mb += 2; }
-            else { rc = conv2d_launch<1, 4, 1, false, true>(a, B, st); mb += 1; }
-        }
-        if (rc) return rc;
-    }
-    return WM_OK;
+    return conv2d_walk<true, false>(a, B, ks, st);
 }
 
 // The training step's convolution (fp16 split): `amax` (two floats; a slot of the caller's zeroed arena skips the memset node) and the
@@ -351,15 +337,10 @@ int wm_conv2d_dwt_fwd(const void* img, const void* wfrag, const float* bias, voi
     if (dtype != WM_F32 || Cout != 32) return WM_EUNSUPPORTED;
     if (B == 0 || H == 0 || W == 0) return WM_OK;
     if (!img || !wfrag || !ll || !hl || !lh || !hh) return WM_ENULL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = (const float*)img; a.xb = nullptr; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
-    a.bias = bias; a.gate = nullptr; a.res = nullptr; a.wfrag1 = nullptr; a.bias1 = nullptr;
-    a.y = (float*)ll; a.yband[0] = (float*)hl; a.yband[1] = (float*)lh; a.yband[2] = (float*)hh;
-    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 0; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = (Cin + 15) / 16; a.mtot = 1; a.mbase = 0; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    Conv2dArgs a = conv_args(img, Cin, wfrag, bias, ll, Cout, H, W);        // (Cout = 32: one row tile, mbase stays 0)
+    a.yband[0] = (float*)hl; a.yband[1] = (float*)lh; a.yband[2] = (float*)hh;
     // the kernel's 32-bit byte offsets inside one batch element of the input and of the full-resolution output it stands for
     if (conv_select_mode() == 1 || (long long)std::max(Cin, Cout) * H * W * 4 >= (1ll << 32)) return WM_EUNSUPPORTED;
     ProfScope ps(13, st);
@@ -375,14 +356,11 @@ int wm_idwt_conv2d_fwd(const void* low, const void* high, const void* wfrag, con
     if (dtype != WM_F32 || Cin != 32) return WM_EUNSUPPORTED;
     if (B == 0 || H == 0 || W == 0) return WM_OK;
     if (!low || !high || !wfrag || !y) return WM_ENULL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = (const float*)low; a.xb = (const float*)high; a.xb_idx = nullptr; a.wfrag = (const uint4*)wfrag;
-    a.bias = bias; a.gate = nullptr; a.res = residual; a.y = y; a.wfrag1 = nullptr; a.bias1 = nullptr;
-    a.Ca = Cin; a.Cb = 0; a.Cbsrc = 3 * Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = Cin / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    Conv2dArgs a = conv_args(low, Cin, wfrag, bias, y, Cout, H, W);
+    a.xb = (const float*)high; a.Cbsrc = 3 * Cin;            // the bands feed the same Cin / 16 chunks: Cb stays 0 and nch as built
+    a.res = residual;
     // 32-bit byte offsets inside one batch element of `high` (3 Cin planes of H W / 4), of y and of the residual
     if (conv_select_mode() == 1 || (long long)std::max(Cin, Cout) * H * W * 4 >= (1ll << 32)) return WM_EUNSUPPORTED;
     ProfScope ps(13, st);
@@ -403,14 +381,13 @@ int wm_conv2d_gated_fwd(const float* xa, const float* xb, const int* xb_index, c
     if (!xa || !wfrag3 || !wfrag1 || !y || (Cb > 0 && !xb)) return WM_ENULL;
     if (Cb > 0 && Ca % 8 != 0) return WM_EUNSUPPORTED;
     if (Cb > 0 && !xb_index && Cb_src != Cb) return WM_EINVAL;
-    if (B > 65535 || (long long)H * W >= (1ll << 31)) return WM_EUNSUPPORTED;
-    if (!aligned16(wfrag3) || !aligned16(wfrag1)) return WM_EALIGN;
+    if (const int rc = conv_tail_check(B, H, W, wfrag3)) return rc;
+    if (!aligned16(wfrag1)) return WM_EALIGN;
     hipStream_t st = (hipStream_t)stream;
-    Conv2dArgs a;
-    a.xa = xa; a.xb = Cb > 0 ? xb : nullptr; a.xb_idx = Cb > 0 ? xb_index : nullptr; a.wfrag = (const uint4*)wfrag3;
-    a.bias = nullptr; a.gate = nullptr; a.res = nullptr; a.y = y; a.wfrag1 = (const uint4*)wfrag1; a.bias1 = bias1;
-    a.Ca = Ca; a.Cb = Cb; a.Cbsrc = Cb_src; a.Cout = Cout; a.H = H; a.W = W;
-    a.nch = (Ca + Cb + 15) / 16; a.mtot = (Cout + 31) / 32; a.amax = nullptr; a.ln_w = nullptr; a.ln_b = nullptr; a.ln_eps = 0.0f;
+    Conv2dArgs a = conv_args(xa, Ca, wfrag3, nullptr, y, Cout, H, W);
+    if (Cb > 0) { a.xb = xb; a.xb_idx = xb_index; }
+    a.Cb = Cb; a.Cbsrc = Cb_src; a.nch = (Ca + Cb + 15) / 16;
+    a.wfrag1 = (const uint4*)wfrag1; a.bias1 = bias1;
     ProfScope ps(13, st);
     for (int mb = 0; mb < a.mtot;) {
         // two accumulator sets per wave: 64 channels x 8-row tiles read the input once (0.79 ms against 0.90 ms for

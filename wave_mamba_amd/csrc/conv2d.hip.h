@@ -46,25 +46,25 @@ using f32x16_t = __attribute__((ext_vector_type(16))) float;
 constexpr int kCvTW = 32;             // tile width in pixels = one MFMA column tile
 
 struct Conv2dArgs {
-    const float* xa;                  // input channels [0, Ca)      (B, Ca, H, W)
-    const float* xb;                  // input channels [Ca, Ca+Cb): (B, Cbsrc, H, W) or null - cat([xa, xb'], 1) fused
-    const int* xb_idx;                // (B, Cb) or null: channel Ca + c is xb[b, xb_idx[b, c]] (torch.gather fused)
-    const uint4* wfrag;               // conv2d_prep_kernel output
-    const float* bias;                // (Cout) or null
-    const float* gate;                // (B, Cout, H, W) or null: out *= sigmoid(gate)
-    const float* res;                 // (B, Cout, H, W) or null: out += res
-    const uint4* wfrag1;              // G1X1 kernels: prepared 1x1 weights over the same input (PAConv.k2), else unused
-    const float* bias1;               // G1X1: bias of that 1x1 (or null)
-    float* y;                         // (B, Cout, H, W)
+    const float* xa = nullptr;        // input channels [0, Ca)      (B, Ca, H, W)
+    const float* xb = nullptr;        // input channels [Ca, Ca+Cb): (B, Cbsrc, H, W) or null - cat([xa, xb'], 1) fused
+    const int* xb_idx = nullptr;      // (B, Cb) or null: channel Ca + c is xb[b, xb_idx[b, c]] (torch.gather fused)
+    const uint4* wfrag = nullptr;     // conv2d_prep_kernel output
+    const float* bias = nullptr;      // (Cout) or null
+    const float* gate = nullptr;      // (B, Cout, H, W) or null: out *= sigmoid(gate)
+    const float* res = nullptr;       // (B, Cout, H, W) or null: out += res
+    const uint4* wfrag1 = nullptr;    // G1X1 kernels: prepared 1x1 weights over the same input (PAConv.k2), else unused
+    const float* bias1 = nullptr;     // G1X1: bias of that 1x1 (or null)
+    float* y = nullptr;               // (B, Cout, H, W)
     float* yband[3] = {nullptr, nullptr, nullptr};   // analysis epilogue (conv2d_ws.hip.h, DWTE): y = LL and these HL, LH, HH, each (B, Cout, H / 2, W / 2)
-    int Ca, Cb, Cbsrc, Cout, H, W;
-    int nch;                          // ceil((Ca + Cb) / 16) input-channel chunks
-    int mtot;                         // ceil(Cout / 32) row tiles in wfrag
-    int mbase;                        // first row tile of this launch
-    const float* amax;                // F16 kernels: device floats {max |input|, max |weight|} (the power-of-two operand scales), else null
-    const float* ln_w;                // LNIN kernels (1x1, Ca == 32, no second input): LayerNorm2d over the 32 input channels of a pixel
-    const float* ln_b;                //   applied while the pixel is staged: y = conv1x1(weight * (x - mean) / sqrt(var + eps) + bias)
-    float ln_eps;
+    int Ca = 0, Cb = 0, Cbsrc = 0, Cout = 0, H = 0, W = 0;
+    int nch = 0;                      // ceil((Ca + Cb) / 16) input-channel chunks
+    int mtot = 0;                     // ceil(Cout / 32) row tiles in wfrag
+    int mbase = 0;                    // first row tile of this launch
+    const float* amax = nullptr;      // F16 kernels: device floats {max |input|, max |weight|} (the power-of-two operand scales), else null
+    const float* ln_w = nullptr;      // LNIN kernels (1x1, Ca == 32, no second input): LayerNorm2d over the 32 input channels of a pixel
+    const float* ln_b = nullptr;      //   applied while the pixel is staged: y = conv1x1(weight * (x - mean) / sqrt(var + eps) + bias)
+    float ln_eps = 0.0f;
 };
 
 union Frag16 {

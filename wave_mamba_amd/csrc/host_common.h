@@ -77,6 +77,8 @@ WM_HIDDEN int det_finish(const float* part, long long nblk, long long K, const D
 // > 64 KB of dynamic LDS is an opt-in per kernel function AND per device: one flag per (instantiation, device).
 // `flags` is the caller's function-local static array; returns WM_OK or WM_EHIP.
 WM_HIDDEN int lds_optin(const void* fn, int bytes, bool (&flags)[64]);
+// compute units of the current device (asked once per device); returns WM_OK or WM_EHIP
+WM_HIDDEN int device_cus(int* ncu);
 
 }  // namespace wm
 

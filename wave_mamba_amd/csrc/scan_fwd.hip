@@ -257,23 +257,10 @@ static int core_plan(CorePlan& pl, int B, int D, int H, int W, int N, int R, int
 template <int NP, int NW, bool RHI, typename TP, bool VEC>
 static int core_launch(const CoreArgs& a, const CorePlan& pl, bool do_prep, hipStream_t st) {
     constexpr int lds = core_lds_bytes<NP, NW>();
-    // > 64 KB of dynamic LDS is an opt-in per function AND per device
-    static bool configured[64] = {};
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return WM_EHIP;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64 || !configured[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)ss2d_core_kernel<NP, NW, 1, RHI, TP, VEC>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)ss2d_core_kernel<NP, NW, 3, RHI, TP, VEC>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return WM_EHIP;
-            if (dev >= 0 && dev < 64) configured[dev] = true;
-        }
-    }
+    static bool configured1[64] = {}, configured3[64] = {};     // the reduce pass (phase 1) and the scan pass (phase 3)
+    int rc = lds_optin((const void*)ss2d_core_kernel<NP, NW, 1, RHI, TP, VEC>, lds, configured1);
+    if (!rc) rc = lds_optin((const void*)ss2d_core_kernel<NP, NW, 3, RHI, TP, VEC>, lds, configured3);
+    if (rc) return rc;
     const dim3 grid((unsigned)(a.B * (2 * pl.row_wgs + 2 * pl.col_wgs))), block(64 * NW);
     const bool split = pl.row_nchunks > 1 || pl.col_nchunks > 1;
     if (do_prep) {   // parameters -> bf16 weight fragments, A * log2(e), per-channel constants (four small blocks)
