@@ -8,7 +8,17 @@ GraphedTrainStep, schedulers, ops.psnr_ssim_y).
 
     python -m wave_mamba_amd.recipe -opt FILE --train-pairs DIR [--val-pairs DIR] [--eager] [--out-dir DIR]
 
-Single process: `rank` and `world` reach the sampler and the seeds only (the data-parallel GraphedDDPTrainStep is not wired in).
+    torchrun --nproc_per_node N -m wave_mamba_amd.recipe -opt FILE --train-pairs DIR ... [--dist-backend nccl|gloo] [--collective split|captured]
+
+Data-parallel training (the reference's `--launcher pytorch`).  Under an initialised torch.distributed group of more than one rank
+(or with distributed=True, on a one-rank group too) the step is trainer.GraphedDDPTrainStep on the bare module - graph A, one flat
+all-reduce, graph B; its eager form when the loop is not graphed - and the loop keeps its promises across ranks: the constructor's
+warm-up is undone on every rank (rank 0's parameters are broadcast BEFORE the snapshot), rank 0 alone writes train.log, models/ and
+training_states/, the logged losses are the mean over ranks, a state holds every rank's batcher random state (collected
+collectively when it is saved) and resumes exactly at its own world size, and validation is sharded: rank r scores pairs r,
+r + world, ... into its rows of an (n, borders, 2) float64 matrix, one all-reduce (sum) fills in the zero rows and every rank adds
+the rows in store order - the single-process score bit for bit, the same best-model decision on every rank.  Every rank holds the
+whole stores.  Without a group `rank` and `world` reach the sampler and the seeds only.
 Out of scope: decoding image files (pairs are uint8 arrays), TensorBoard / wandb, LPIPS (skipped with a warning), saving
 validation images.
 
@@ -27,6 +37,7 @@ import math
 import os
 
 import torch
+import torch.distributed as dist
 
 from . import schedulers, trainer
 from .data import DeviceImageStore, PairedPatchBatcher
@@ -174,7 +185,7 @@ def _freq(value):
 
 
 class Trainer:
-    """The reference's train_pipeline for one process.
+    """The reference's train_pipeline, for one process or for one rank of a torch.distributed group.
 
     opt          the recipe: a dict, a file name or YAML text (load_options)
     train_store  data.DeviceImageStore of the training pairs, on the device to train on (a 'cpu' store trains on the CPU)
@@ -183,6 +194,12 @@ class Trainer:
                  False (and always on the CPU): train_step(..., as_float=False)
     step_fn      step_fn(lq, gt) -> {name: 0-dim tensor} in place of the step (tests)
     net          a ready network in place of build_network(opt["network_g"])
+    distributed  None: the data-parallel mode (module docstring) is on exactly when torch.distributed is initialised with more than
+                 one rank; True forces it on a one-rank group (the RCCL self-test; ValueError without a group); False: off
+    process_group, collective   GraphedDDPTrainStep's (files are written by the group's rank 0, which save_network expects to be
+                 the global rank 0)
+    rank, world  in the mode they come from the group (explicit values that contradict it: ValueError); otherwise None reads as
+                 0 / 1 and explicit values reach the sampler and the seeds only
 
     run(max_iters=None, on_iter=None) trains to the recipe's end; `max_iters` pauses after that many iterations (no end-of-training
     save / validation then; run() again continues).  on_iter(current_iter, epoch, lrs, rows, losses) is called after every step:
@@ -190,13 +207,26 @@ class Trainer:
     net_g_latest.pth, net_g_best_{iter}.pth (net_g_best_.pth without a key metric), out_dir/training_states/{iter}.state,
     out_dir/train.log (one JSON object per line; the same lines go to the `wave_mamba_amd` logger)."""
 
-    def __init__(self, opt, train_store, val_store=None, device=None, graphed=True, out_dir=".", rank=0, world=1, step_fn=None,
-                 net=None):
+    def __init__(self, opt, train_store, val_store=None, device=None, graphed=True, out_dir=".", rank=None, world=None, step_fn=None,
+                 net=None, distributed=None, process_group=None, collective="split"):
         if not isinstance(opt, dict):
             opt, _ = load_options(opt)
         else:
             check_options(opt)
-        self.opt, self.train_store, self.val_store, self.rank, self.world = opt, train_store, val_store, int(rank), int(world)
+        ready = dist.is_available() and dist.is_initialized()
+        if distributed is None:
+            distributed = ready and dist.get_world_size(process_group) > 1
+        elif distributed and not ready:
+            raise ValueError("distributed: True needs an initialised torch.distributed process group")
+        self.distributed, self.group, self.collective = bool(distributed), process_group, collective
+        if self.distributed:
+            for name, given, have in (("rank", rank, dist.get_rank(process_group)), ("world", world, dist.get_world_size(process_group))):
+                if given is not None and int(given) != have:
+                    raise ValueError(f"{name}: {given!r} contradicts the process group, where it is {have}")
+            rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
+        self.opt, self.train_store, self.val_store = opt, train_store, val_store
+        self.rank, self.world = int(rank or 0), int(1 if world is None else world)
+        self.writer = not self.distributed or self.rank == 0          # the rank that owns train.log, models/ and training_states/
         self.device = torch.device(device) if device is not None else train_store.device
         if self.device != train_store.device or (val_store is not None and val_store.device != self.device):
             raise ValueError(f"Trainer: the stores must live on the training device {self.device}")
@@ -249,50 +279,85 @@ class Trainer:
             self._resume(resume_state, pretrained)
         elif pretrained:
             trainer.load_network(self.net, pretrained, strict=bool(_get(opt, "path.strict_load", True)))
+        if self.distributed:                                       # seeds differ by rank: rank 0's initialisation is the run's
+            trainer.broadcast_parameters(self.net, self.group)
 
     # -- resume ---------------------------------------------------------------------------------------------------------------------
     def _resume(self, path, pretrained):
         """train.py:159-163 + base_model.py:359-373.  The weights come from path.pretrain_network_g or, without one, from
         models/net_g_{iter}.pth beside the state's folder (the layout this class writes).  With the state's "recipe" entry the
         run continues exactly: position inside the epoch and the batcher's random state; without one (a state the reference
-        wrote) the epoch restarts at its first batch with a fresh random state, as in the reference."""
+        wrote) the epoch restarts at its first batch with a fresh random state, as in the reference.  A state written in the
+        distributed mode also names its world size and holds one random state per rank: it continues exactly at that world size,
+        every rank taking its own; at another one, or in a single process - and a single-process state in the mode - the epoch
+        restarts like a reference state's (its batches are other ones)."""
         state = torch.load(path, map_location="cpu", weights_only=True)
         epoch, current_iter = trainer.resume_training(state, [self.optimizer], [self.scheduler])
         weights = pretrained or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "models", f"net_g_{current_iter}.pth")
         trainer.load_network(self.net, weights, strict=bool(_get(self.opt, "path.strict_load", True)) if pretrained else True)
         self.epoch, self.current_iter = int(epoch), int(current_iter)
         extra = state.get("recipe")
-        if extra is not None:
+        exact = extra is not None and extra.get("world") == (self.world if self.distributed else None)
+        if exact:
             self._pos = int(extra["batch"])
-            rng = extra["rng"]
+            rng = extra["rngs"][self.rank] if self.distributed else extra["rng"]
             self.batcher.rng.setstate((rng[0], tuple(rng[1]), rng[2]))
-        self._log({"resumed": path, "epoch": self.epoch, "iter": self.current_iter, "exact": extra is not None})
+        self._log({"resumed": path, "epoch": self.epoch, "iter": self.current_iter, "exact": exact})
 
     # -- logging / files ------------------------------------------------------------------------------------------------------------
     def _log(self, record, level=logging.INFO):
         line = json.dumps(record)
-        os.makedirs(self.out_dir, exist_ok=True)
-        with open(os.path.join(self.out_dir, "train.log"), "a", encoding="utf-8") as f:
-            f.write(line + "\n")
+        if self.writer:
+            os.makedirs(self.out_dir, exist_ok=True)
+            with open(os.path.join(self.out_dir, "train.log"), "a", encoding="utf-8") as f:
+                f.write(line + "\n")
         LOG.log(level, line)
 
     def _model_path(self, label):
         return os.path.join(self.out_dir, "models", f"net_g_{label}.pth")
 
+    def _save_network(self, label, current_iter, epoch):
+        if self.writer:
+            trainer.save_network(self.net, self._model_path(label), current_iter, epoch)
+
+    def _all_rng_states(self):
+        """Every rank's batcher random state, on every rank: each rank fills its row of a (world, 624 + 1) int64 matrix and one
+        all-reduce (sum) fills in the others' (the collective both backends have for device and host tensors alike)."""
+        version, words, gauss = self.batcher.rng.getstate()
+        if gauss is not None:
+            raise RuntimeError("Trainer: the batcher's random state holds a pending gauss() value; only randint() is drawn from it")
+        mat = torch.zeros((self.world, len(words)), dtype=torch.int64, device=self.device)
+        mat[self.rank] = torch.tensor(words, dtype=torch.int64)
+        dist.all_reduce(mat, op=dist.ReduceOp.SUM, group=self.group)
+        return [(version, tuple(row), None) for row in mat.tolist()]
+
     def save(self, epoch, current_iter):
-        """model.save(): base_model.py:227-228 and :341-342 name the files."""
-        trainer.save_network(self.net, self._model_path("latest" if current_iter == -1 else current_iter), current_iter, epoch)
-        trainer.save_training_state(os.path.join(self.out_dir, "training_states", f"{current_iter}.state"), epoch, current_iter,
-                                    [self.optimizer], [self.scheduler],
-                                    extra={"batch": self._pos, "rng": self.batcher.rng.getstate()})
+        """model.save(): base_model.py:227-228 and :341-342 name the files.  In the distributed mode a collective: every rank
+        calls it, rank 0 writes."""
+        extra = {"batch": self._pos, "rng": self.batcher.rng.getstate()}
+        if self.distributed:
+            extra = {"world": self.world, "batch": self._pos, "rngs": self._all_rng_states()}
+        self._save_network("latest" if current_iter == -1 else current_iter, current_iter, epoch)
+        if self.writer:
+            trainer.save_training_state(os.path.join(self.out_dir, "training_states", f"{current_iter}.state"), epoch, current_iter,
+                                        [self.optimizer], [self.scheduler], extra=extra)
 
     # -- the step ---------------------------------------------------------------------------------------------------------------------
     def _capture(self, lq, gt):
-        """GraphedTrainStep on (lq, gt) whose three warm-up steps leave no trace (see the module docstring)."""
+        """GraphedTrainStep on (lq, gt) whose three warm-up steps leave no trace (see the module docstring).  Distributed mode:
+        GraphedDDPTrainStep, captured when the loop is graphed and in its eager form otherwise.  Its constructor broadcasts rank
+        0's parameters before it warms up, so the broadcast comes first here: a snapshot taken before it would put a rank's own
+        weights back."""
+        if self.distributed:
+            trainer.broadcast_parameters(self.net, self.group)
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         weights = {k: v.detach().clone() for k, v in self.net.state_dict().items()}
         moments = {p: {k: v.clone() for k, v in st.items() if isinstance(v, torch.Tensor)} for p, st in self.optimizer.state.items()}
-        step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
+        if self.distributed:
+            step = trainer.GraphedDDPTrainStep(self.net, self.optimizer, lq, gt, process_group=self.group, capture=self.graphed,
+                                               collective=self.collective, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
+        else:
+            step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
         with torch.no_grad():
             for k, v in self.net.state_dict().items():
                 v.copy_(weights[k])
@@ -304,7 +369,7 @@ class Trainer:
         return step
 
     def _step(self, rows):
-        if self.graphed:
+        if self.graphed or (self.distributed and self.step_fn is None):
             if self._gstep is None:
                 self._gstep = self._capture(*self.batcher.form(rows=rows))
                 self._run_graphed = trainer.graphed_step_with_batcher(self._gstep, self.batcher)
@@ -333,29 +398,37 @@ class Trainer:
         tensor2img quantisation, the Y-channel PSNR / SSIM with the metric's crop_border, net.train() (femasr_model.py:187-199,
         :229-275).  On a GPU the per-image scores are summed on the device in float64, in store order, and read once."""
         borders = sorted({m["crop_border"] for m in self.metrics.values()})
-        sums, n = {c: None for c in borders}, len(self.val_store)
-        for i in range(n):
+        n = len(self.val_store)
+        if not borders:
+            return {}
+        # (n, borders, 2): a pair's scores per border.  Distributed mode: rank r scores pairs r, r + world, ..., the other rows stay
+        # zero and one all-reduce (sum) fills them in - adding zeros is exact, so every rank then holds the single-process rows
+        rows = torch.zeros((n, len(borders), 2), dtype=torch.float64, device=self.device)
+        for i in range(self.rank, n, self.world) if self.distributed else range(n):
             lq, gt = self.val_store.pair(i)
             self.net.eval()
             res = self._enhance_u8(lq)
             self.net.train()
-            for c in borders:
+            for j, c in enumerate(borders):
                 if res.is_cuda:
                     from . import ops
-                    pair = ops.psnr_ssim_y(res, gt, c, layout="HWC", bgr=True)[0]
+                    rows[i, j] = ops.psnr_ssim_y(res, gt, c, layout="HWC", bgr=True)[0]
                 else:
                     from .metrics import psnr_ssim_y_cpu
-                    pair = torch.tensor(psnr_ssim_y_cpu(res, gt, c, "HWC", True), dtype=torch.float64)
-                sums[c] = pair if sums[c] is None else sums[c] + pair
-        host = dict(zip(borders, torch.stack([sums[c] for c in borders]).tolist())) if borders else {}
+                    rows[i, j] = torch.tensor(psnr_ssim_y_cpu(res, gt, c, "HWC", True), dtype=torch.float64)
+        if self.distributed:
+            dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=self.group)
+        total = rows[0]
+        for i in range(1, n):                                       # one row after the other, in store order: not a tree sum
+            total = total + rows[i]
+        host = dict(zip(borders, total.tolist()))
         return {name: host[m["crop_border"]][0 if m["type"] == "psnr" else 1] / n for name, m in self.metrics.items()}
 
     def validate(self, current_iter, epoch):
         """One validation: scores, best bookkeeping, the best checkpoint, one log line.  -> the result dict."""
         results = self.score()
         if self.best.update(results, current_iter, self.key_metric):
-            trainer.save_network(self.net, self._model_path(f"best_{current_iter}" if self.key_metric is not None else "best_"),
-                                 current_iter, epoch)
+            self._save_network(f"best_{current_iter}" if self.key_metric is not None else "best_", current_iter, epoch)
         self._log({"iter": current_iter, "epoch": epoch, "validation": results,
                    "best": {k: {"val": r["val"], "iter": r["iter"]} for k, r in self.best.records.items()}})
         return results
@@ -392,7 +465,7 @@ class Trainer:
                 break
             self.epoch, self._pos = self.epoch + 1, 0
         self._finished = True
-        trainer.save_network(self.net, self._model_path("latest"), -1, -1)             # model.save(epoch=-1, current_iter=-1)
+        self._save_network("latest", -1, -1)                                           # model.save(epoch=-1, current_iter=-1)
         last = self.validate(self.current_iter, self.epoch) if self.val_freq else None
         self._log({"end_of_training": True, "iter": self.current_iter})
         return {"iter": self.current_iter, "epoch": self.epoch, "finished": True, "validation": last}
@@ -420,15 +493,36 @@ def main(argv=None):
     ap.add_argument("--val-pairs", default=None)
     ap.add_argument("--eager", action="store_true", help="train_step per iteration instead of one graph replay")
     ap.add_argument("--out-dir", default="experiments")
-    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--device", default=None, help="default: cuda:0, under torchrun cuda:LOCAL_RANK")
     ap.add_argument("--max-iters", type=int, default=None, help="pause after this many iterations")
+    ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default=None, help="under torchrun; default: nccl on a GPU, gloo on the CPU")
+    ap.add_argument("--collective", choices=("split", "captured"), default="split",
+                    help="under torchrun, graphed: the all-reduce between two graph replays, or inside one graph (nccl only)")
+    ap.add_argument("--dist-timeout", type=float, default=1800.0,
+                    help="seconds after which a collective whose peer is gone ends with an error instead of waiting on")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
-    train = load_pairs(args.train_pairs, args.device)
-    val = load_pairs(args.val_pairs, args.device) if args.val_pairs else None
-    opt, _ = load_options(args.opt, num_train=len(train))
-    result = Trainer(opt, train, val, graphed=not args.eager, out_dir=args.out_dir).run(max_iters=args.max_iters)
-    print(json.dumps(result))
+    env = os.environ
+    launched = all(k in env for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK")) and int(env["WORLD_SIZE"]) > 1
+    device = torch.device(args.device or (f"cuda:{env['LOCAL_RANK']}" if launched else "cuda:0"))
+    if launched:
+        import datetime
+        backend = args.dist_backend or ("nccl" if device.type == "cuda" else "gloo")
+        if device.type == "cuda":
+            torch.cuda.set_device(device)
+        dist.init_process_group(backend, timeout=datetime.timedelta(seconds=args.dist_timeout),
+                                **({"device_id": device} if backend == "nccl" else {}))
+    try:
+        train = load_pairs(args.train_pairs, device)
+        val = load_pairs(args.val_pairs, device) if args.val_pairs else None
+        opt, _ = load_options(args.opt, num_train=len(train))
+        t = Trainer(opt, train, val, graphed=not args.eager, out_dir=args.out_dir, collective=args.collective)
+        result = t.run(max_iters=args.max_iters)
+        if t.writer:
+            print(json.dumps(result))
+    finally:
+        if launched:
+            dist.destroy_process_group()
     return 0
 
 

@@ -176,6 +176,14 @@ class GraphedTrainStep:
         return self.losses
 
 
+def broadcast_parameters(net, process_group=None):
+    """DDP's constructor: every rank of the group takes rank 0's parameters and buffers, in place."""
+    src = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+    with torch.no_grad():
+        for t in list(net.parameters()) + list(net.buffers()):
+            dist.broadcast(t, src=src, group=process_group)
+
+
 class GraphedDDPTrainStep:
     """The data-parallel optimize_parameters() (femasr_model.py:157-185 under the DistributedDataParallel wrap of
     base_model.py:111-114) with the host taken out of the step: every rank replays
@@ -194,11 +202,12 @@ class GraphedDDPTrainStep:
                     kernels and capture like any other launch)
     `capture=False` runs the same three phases eagerly - what the CPU / gloo tests exercise, and the cross-check of the replays.
     Fixed batch shape; `optimizer` as for GraphedTrainStep on a GPU.  `ssim_weight`: the weighted SSIM term joins the sum and
-    rides in the buffer as a third loss.  Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`): 0-dim tensors holding the
+    rides in the buffer as a third loss; `fft_weight`: the recipe's fft_opt.loss_weight, as in GraphedTrainStep.  Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`): 0-dim tensors holding the
     MEAN over ranks of the step just run (every rank has them - they ride in the gradient buffer; the reference's
     reduce_loss_dict, base_model.py:376-401, leaves them on rank 0 only)."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split", ssim_weight=None):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split", ssim_weight=None,
+                 fft_weight=0.1):
         if isinstance(net, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)):
             raise RuntimeError("GraphedDDPTrainStep: pass the bare module, not its DistributedDataParallel wrap")
         if not (dist.is_available() and dist.is_initialized()):
@@ -208,7 +217,7 @@ class GraphedDDPTrainStep:
         self.group = process_group
         self.world = dist.get_world_size(process_group)
         self.net, self.optimizer, self.capture, self.collective = net, optimizer, capture, collective
-        self.ssim_weight = ssim_weight
+        self.ssim_weight, self.fft_weight = ssim_weight, fft_weight
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         if capture:
             if not all(p.is_cuda for p in self.params):
@@ -218,11 +227,7 @@ class GraphedDDPTrainStep:
                 raise RuntimeError("GraphedDDPTrainStep: the optimizer must be make_optimizer(net, capturable=True)")
             if collective == "captured" and dist.get_backend(process_group) != "nccl":
                 raise RuntimeError("GraphedDDPTrainStep: collective='captured' needs the nccl (RCCL) backend")
-        # DDP's constructor: every rank starts from rank 0's parameters and buffers
-        with torch.no_grad():
-            for t in list(net.parameters()) + list(net.buffers()):
-                dist.broadcast(t, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0,
-                               group=process_group)
+        broadcast_parameters(net, process_group)
         dev = self.params[0].device
         self.sizes = [p.numel() for p in self.params]
         nl = 2 if ssim_weight is None else 3
@@ -262,7 +267,7 @@ class GraphedDDPTrainStep:
         for p in self.params:
             p.grad = None
         out = self.net(self.lq)
-        terms = losses(out, self.gt, ssim_weight=self.ssim_weight)
+        terms = losses(out, self.gt, fft_weight=self.fft_weight, ssim_weight=self.ssim_weight)
         _total(terms).backward()
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in self.params]
         torch._foreach_copy_(self.views, grads)
