@@ -11,6 +11,10 @@ three levels' maps are 32 x 64, 16 x 32 and 8 x 16: levels 1 and 2 take lfss_blo
 level 3 the unfused pair, and the side streams run.
 
 Usage:  python tests/golden/make_golden_dispatch.py <commit the working tree is at> [output file]
+        python tests/golden/make_golden_dispatch.py <commit> --only MODE
+The second form re-records ONE mode's line of the committed file - for a change that corrects that mode's dispatch on purpose - and
+names the commit in a `MODE_recorded_on` key; every other line stays byte for byte.  (`frozen_input_grad` was re-recorded so with the
+fold of CMTAttention.forward asking about its inputs too: the list of 4cb310b recorded attn_fold taken under autograd.)
 """
 import json
 import os
@@ -66,9 +70,31 @@ def run_mode(mode):
     torch.cuda.synchronize()
 
 
+def record_only(mode, commit):
+    """Replace the line of `mode` in the committed file and set `<mode>_recorded_on`."""
+    import wave_mamba_amd as wm
+    from wave_mamba_amd.archs import wavemamba_arch as arch
+    assert mode in MODES, mode
+    rec = Recorder(wm.ops)
+    arch._OpsBackend.impl = rec
+    try:
+        run_mode(mode)
+    finally:
+        arch._OpsBackend.impl = wm.ops
+    with open(OUT) as f:
+        lines = [ln.rstrip(",") for ln in f.read().split("\n")[1:-2] if not ln.startswith(json.dumps(mode + "_recorded_on"))]
+    at = next(i for i, ln in enumerate(lines) if ln.startswith(json.dumps(mode) + ":"))
+    lines[at:at + 1] = [f"{json.dumps(mode)}: {json.dumps(rec.calls)}", f"{json.dumps(mode + '_recorded_on')}: {json.dumps(commit)}"]
+    with open(OUT, "w") as f:
+        f.write("{\n" + ",\n".join(lines) + "\n}\n")
+    print(f"{mode}: {len(rec.calls)} calls, {len(set(rec.calls))} operators; rewrote that line of {OUT}")
+
+
 def main():
     import wave_mamba_amd as wm
     from wave_mamba_amd.archs import wavemamba_arch as arch
+    if len(sys.argv) == 4 and sys.argv[2] == "--only":
+        return record_only(sys.argv[3], sys.argv[1])
     out = {"recorded_on": sys.argv[1]}
     for mode in MODES:
         rec = Recorder(wm.ops)

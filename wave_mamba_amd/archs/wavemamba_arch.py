@@ -671,10 +671,12 @@ class CMTAttention(nn.Module):
         if _op("gram") and ops.gram_supported(q, k) and (not train_gram or _op("gram_train")):
             # normalize(q) @ normalize(k)^T == (q @ k^T) / (max(|q|, eps) max(|k|, eps)): one pass over q, k
             G, nq, nk = ops.gram_train(q, k) if train_gram else ops.gram(q.contiguous(), k.contiguous())
-            # (the fold is forward-only and asks about the module's PARAMETERS alone, as it always has: with every parameter
-            # frozen it is taken for q, k, v under autograd too, and no gradient reaches them through this attention)
+            # (the fold is forward-only - attn_fold and the kernels that apply the folded weight write fresh memory, and the block's
+            # `x + attn(...)` rides inside them: it is taken only when NOTHING that flows into it wants a gradient, neither a
+            # parameter of this module nor q, k, the value operand or the residual.  With the module frozen and, say, norm1
+            # or the input trainable, q / k / v require grad and the autograd composition below carries their graph.)
             if (_op("attn_fold") and ops.attn_fold_supported(x, self.project_out.weight, heads)
-                    and not _needs_grad(self)):
+                    and not _needs_grad(self, q, k, v if pre is None else pre, residual)):
                 # project_out(softmax(...) @ v) = (W_po @ blockdiag(attn)) @ v: a tiny kernel folds the (c/heads)^2
                 # attention into the 1x1 weight, the 1x1 convolution kernel applies it (+ bias, + residual)
                 wf = ops.attn_fold(G, nq, nk, self.temperature.reshape(heads), self.project_out.weight, b, heads)
