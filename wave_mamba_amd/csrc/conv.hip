@@ -230,17 +230,15 @@ int wm_dwconv_conv1x1_fwd(const float* x, int64_t x_batch_stride, const float* d
     DwPwArgs a;
     a.x = x; a.xbs = x_batch_stride; a.dw_w = dw_weight; a.dw_b = dw_bias; a.wfrag = (const uint4*)wfrag; a.bias = bias;
     a.res = residual; a.y = y; a.H = H; a.W = W;
-    a.nstrips = (W + kCvTW - 1) / kCvTW;
     // rows per band (a band re-reads two input rows and re-forms their taps): the tallest of 16, 8, 4 that still gives every SIMD of
     // a 256-unit chip a wave (UHD level 1: 4080 walks of 16 rows, level 2: 2040 of 8, level 3: 1020 of 4)
-    a.rows = 4;
-    for (int rows = 16; rows > 4; rows >>= 1)
-        if ((long long)B * a.nstrips * ((H + rows - 1) / rows) >= 1024) { a.rows = rows; break; }
-    a.nbands = (H + a.rows - 1) / a.rows;
-    a.nwalks = (long long)B * a.nbands * a.nstrips;
-    const long long nblocks = ((a.nwalks + 3) / 4 + 7) / 8 * 8;       // a multiple of 8: the kernel deals contiguous runs to the XCDs
-    if (nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
-    const dim3 grid((unsigned)nblocks);
+    int rows = 4;
+    for (int r = 16; r > 4; r >>= 1)
+        if (row_walk_geom(B, H, W, kCvTW, r, 4, true).nwalks >= 1024) { rows = r; break; }
+    const RowWalkGeom g = row_walk_geom(B, H, W, kCvTW, rows, 4, true);
+    a.nstrips = g.nstrips; a.nbands = g.nbands; a.rows = g.rows; a.nwalks = g.nwalks;
+    if (g.nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
+    const dim3 grid((unsigned)g.nblocks);
     ProfScope ps(14, st);
     if (act == 2) {
         if (residual) hipLaunchKernelGGL((dw_pw_kernel<true, true>), grid, dim3(256), 0, st, a);
@@ -268,17 +266,15 @@ int wm_ln_conv1x1_dwconv_fwd(const float* x, const float* ln_weight, const float
     PwDwArgs a;
     a.x = x; a.ln_w = ln_weight; a.ln_b = ln_bias; a.ln_eps = ln_eps; a.wfrag = (const uint4*)wfrag; a.bias = bias;
     a.dw_w = dw_weight; a.dw_b = dw_bias; a.y = y; a.H = H; a.W = W;
-    a.nstrips = (W + kPwDwCols - 1) / kPwDwCols;
     // rows per band (a band recomputes two x rows of its neighbours): 8 where that still deals every SIMD of a 256-unit chip two
     // walks, else 4 - UHD levels 1 and 2: 8704 / 2176 walks of 8 rows, level 3: 1088 of 4.  Taller bands measured slower at every
     // level, by up to a third: at 2176 walks of 32 rows level 1 is 544 workgroups for the 512 the chip holds at two waves per SIMD -
     // a second, nearly empty round (tools/bench_hfe_heads.py --band-rows, profiles/hfe_heads/per_call_band_rows.txt)
-    a.rows = band_rows ? band_rows : ((long long)B * a.nstrips * ((H + 7) / 8) >= 2048 ? 8 : 4);
-    a.nbands = (H + a.rows - 1) / a.rows;
-    a.nwalks = (long long)B * a.nbands * a.nstrips;
-    const long long nblocks = ((a.nwalks + 3) / 4 + 7) / 8 * 8;       // a multiple of 8: the kernel deals contiguous runs to the XCDs
-    if (nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
-    const dim3 grid((unsigned)nblocks);
+    const int rows = band_rows ? band_rows : (row_walk_geom(B, H, W, kPwDwCols, 8, 4, true).nwalks >= 2048 ? 8 : 4);
+    const RowWalkGeom g = row_walk_geom(B, H, W, kPwDwCols, rows, 4, true);
+    a.nstrips = g.nstrips; a.nbands = g.nbands; a.rows = g.rows; a.nwalks = g.nwalks;
+    if (g.nblocks >= (1ll << 31)) return WM_EUNSUPPORTED;
+    const dim3 grid((unsigned)g.nblocks);
     ProfScope ps(14, st);
     if (qkv) hipLaunchKernelGGL((pw_dw_kernel<3, 2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((pw_dw_kernel<1, 1>), grid, dim3(256), 0, st, a);

@@ -108,6 +108,21 @@ __device__ __forceinline__ f32x16_t cv_mfma(const Frag16& A, const Frag16& B, f3
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(A.h, B.h, c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.v, B.v, c, 0, 0, 0);
 }
+// the three products of a bf16-split 1x1 chunk in their ONE order: (A_hi, B_hi), (A_hi, B_lo), (A_lo, B_hi)
+__device__ __forceinline__ f32x16_t cv_mma3(const Frag16& Ah, const Frag16& Al, const Frag16& Bh, const Frag16& Bl, f32x16_t c) {
+    c = cv_mfma<false>(Ah, Bh, c);
+    c = cv_mfma<false>(Ah, Bl, c);
+    return cv_mfma<false>(Al, Bh, c);
+}
+// D layout of the 32x32 matrix instructions: accumulator register i of lane l is row cv_acc_row(i) + 4 (l >> 5), column l & 31
+constexpr int cv_acc_row(int i) { return (i & 3) + 8 * (i >> 2); }
+// the bias of a (32 NT)-channel 1x1 in accumulator order, [tile][lane >> 5][register]: four ds_read_b128 per tile and lane (all
+// 256 threads, before the staging barrier; a null bias is zeros)
+template <int NT>
+__device__ __forceinline__ void cv_stage_acc_bias(float* s_bias, const float* __restrict__ bias) {
+    for (int i = threadIdx.x; i < NT * 32; i += 256)
+        s_bias[i] = bias ? bias[32 * (i >> 5) + 4 * ((i >> 4) & 1) + cv_acc_row(i & 15)] : 0.0f;
+}
 
 // fragment item `idx` of the prepared weights (layout: conv2d_prep_kernel)
 template <bool F16>
@@ -381,11 +396,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dArgs a)
                             Frag16 Wh, Wl;
                             Wh.u = s_w1[(m * 2 + 0) * 64 + lane];
                             Wl.u = s_w1[(m * 2 + 1) * 64 + lane];
-                            f32x16_t c1 = acc1[m][j - PAD];
-                            c1 = cv_mfma<false>(Wh, Bh, c1);
-                            c1 = cv_mfma<false>(Wh, Bl, c1);
-                            c1 = cv_mfma<false>(Wl, Bh, c1);
-                            acc1[m][j - PAD] = c1;
+                            acc1[m][j - PAD] = cv_mma3(Wh, Wl, Bh, Bl, acc1[m][j - PAD]);
                         }
                     }
                 }
@@ -483,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dArgs a)
         float bv[16], b1v[G1X1 ? 16 : 1];
         if (a.bias) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) bv[i] = a.bias[min(chb + (i & 3) + 8 * (i >> 2), a.Cout - 1)];
+            for (int i = 0; i < 16; ++i) bv[i] = a.bias[min(chb + cv_acc_row(i), a.Cout - 1)];
         } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) bv[i] = 0.0f;
@@ -491,7 +502,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dArgs a)
         if constexpr (G1X1) {
             if (a.bias1) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) b1v[i] = a.bias1[min(chb + (i & 3) + 8 * (i >> 2), a.Cout - 1)];
+                for (int i = 0; i < 16; ++i) b1v[i] = a.bias1[min(chb + cv_acc_row(i), a.Cout - 1)];
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) b1v[i] = 0.0f;
@@ -508,15 +519,15 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dArgs a)
             float gv[16], rv[16];
             if (a.gate) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) gv[i] = a.gate[oplane + (long long)min(chb + (i & 3) + 8 * (i >> 2), a.Cout - 1) * HW];
+                for (int i = 0; i < 16; ++i) gv[i] = a.gate[oplane + (long long)min(chb + cv_acc_row(i), a.Cout - 1) * HW];
             }
             if (a.res) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) rv[i] = a.res[oplane + (long long)min(chb + (i & 3) + 8 * (i >> 2), a.Cout - 1) * HW];
+                for (int i = 0; i < 16; ++i) rv[i] = a.res[oplane + (long long)min(chb + cv_acc_row(i), a.Cout - 1) * HW];
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int dc = (i & 3) + 8 * (i >> 2);
+                const int dc = cv_acc_row(i);
                 float v = (F16 ? acc[m][r][i] * osc : acc[m][r][i]) + bv[i];
                 if constexpr (G1X1) v = v / (1.0f + __expf(-(acc1[m][r][i] + b1v[i])));
                 if (a.gate) v = v / (1.0f + __expf(-gv[i]));

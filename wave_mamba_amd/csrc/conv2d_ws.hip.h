@@ -400,11 +400,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                             Frag16 Wh, Wl;
                             Wh.u = s_w1[(m * 2 + 0) * 64 + lane];
                             Wl.u = s_w1[(m * 2 + 1) * 64 + lane];
-                            f32x16_t c1 = acc1[m][j - 1];
-                            c1 = cv_mfma<false>(Wh, Bh, c1);
-                            c1 = cv_mfma<false>(Wh, Bl, c1);
-                            c1 = cv_mfma<false>(Wl, Bh, c1);
-                            acc1[m][j - 1] = c1;
+                            acc1[m][j - 1] = cv_mma3(Wh, Wl, Bh, Bl, acc1[m][j - 1]);
                         }
                     }
                 }
@@ -437,7 +433,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 for (int r = 0; r < RW; ++r)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const unsigned o = o0 + (unsigned)(r * W) * 4u + (unsigned)((i & 3) + 8 * (i >> 2)) * HWb;
+                        const unsigned o = o0 + (unsigned)(r * W) * 4u + (unsigned)cv_acc_row(i) * HWb;
                         ev[r][i] = *reinterpret_cast<const float*>(eb + (size_t)o);
                     }
             }
@@ -445,7 +441,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 float bv[16], b1v[G1X1 ? 16 : 1];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int cl = m * 32 + 4 * khalf + (i & 3) + 8 * (i >> 2);
+                    const int cl = m * 32 + 4 * khalf + cv_acc_row(i);
                     bv[i] = s_bias[cl];
                     if (G1X1) b1v[i] = s_bias[MT * 32 + cl];
                 }
@@ -454,7 +450,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 for (int r = 0; r < RW; ++r)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const unsigned o = o0 + (unsigned)(r * W) * 4u + (unsigned)((i & 3) + 8 * (i >> 2)) * HWb;
+                        const unsigned o = o0 + (unsigned)(r * W) * 4u + (unsigned)cv_acc_row(i) * HWb;
                         float v = (F16 ? acc[m][r][i] * osc : acc[m][r][i]) + bv[i];
                         if constexpr (G1X1) v = v / (1.0f + __expf(-(acc1[m][r][i] + b1v[i])));
                         if constexpr (EPI) v = is_gate ? v / (1.0f + __expf(-ev[r][i])) : v + ev[r][i];
@@ -473,7 +469,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 const long long o = (((long long)b * a.Cout + chb) * H + min(h, H - 1)) * W + min(w, W - 1);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int dc = (i & 3) + 8 * (i >> 2);
+                    const int dc = cv_acc_row(i);
                     const bool ok = in && (full || chb + dc < a.Cout);
                     ev[r][i] = ok ? eptr[o + dc * HW] : 0.0f;
                 }
@@ -484,7 +480,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
             float bv[16], b1v[G1X1 ? 16 : 1];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int cl = m * 32 + 4 * khalf + (i & 3) + 8 * (i >> 2);
+                const int cl = m * 32 + 4 * khalf + cv_acc_row(i);
                 bv[i] = s_bias[cl];
                 if (G1X1) b1v[i] = s_bias[MT * 32 + cl];
             }
@@ -495,7 +491,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 const long long o = (((long long)b * a.Cout + chb) * H + h) * W + w;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int dc = (i & 3) + 8 * (i >> 2);
+                    const int dc = cv_acc_row(i);
                     float v = (F16 ? acc[m][r][i] * osc : acc[m][r][i]) + bv[i];
                     if constexpr (G1X1) v = v / (1.0f + __expf(-(acc1[m][r][i] + b1v[i])));
                     if constexpr (EPI) v = is_gate ? v / (1.0f + __expf(-ev[r][i])) : v + ev[r][i];
@@ -525,7 +521,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
         const unsigned o0 = (unsigned)((chb * h2 + hq) * w2 + (w >> 1)) * 4u;
         float bv[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) bv[i] = s_bias[4 * khalf + (i & 3) + 8 * (i >> 2)];
+        for (int i = 0; i < 16; ++i) bv[i] = s_bias[4 * khalf + cv_acc_row(i)];
         auto quads = [&](auto FASTC) {                    // FAST: interior tile, whole row tiles - the store path without predicates
             constexpr bool FAST = decltype(FASTC)::value;
 #pragma unroll
@@ -533,7 +529,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, (4 + NPW) / 4) void conv3x3_ws_kern
                 const bool in = FAST || (h0 + rg * RW + 2 * rp < H && w < W);  // (a quad is inside the image whole or not at all)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int dc = (i & 3) + 8 * (i >> 2);
+                    const int dc = cv_acc_row(i);
                     const float v0 = acc[0][2 * rp][i] + bv[i], v1 = acc[0][2 * rp + 1][i] + bv[i];
                     const float n0 = ws_from_pair_lane(v0), n1 = ws_from_pair_lane(v1);     // (every lane takes part: before the predicate)
                     float ll, hl, lh, hh;

@@ -1,27 +1,25 @@
 // dw_pw.hip.h - a depth-wise 3x3 convolution (+ bias, + optional exact GELU) folded into the 1x1 convolution that is its only
-// reader:  y = conv1x1(act(dwconv3x3(x) + b_dw)) + b_pw (+ residual),  32 -> 32 channels, NCHW fp32, for gfx950.
+// reader:  y = conv1x1(act(dwconv3x3(x) + b_dw)) + b_pw (+ residual),  32 -> 32 channels, NCHW fp32, for gfx950.  One of the
+// row-walking kernels: the scheme, what it costs to keep and the shared pieces are in row_walk.hip.h.
 //
 // Call sites (HFE branch): FeedForward.project_out = [depth-wise 3x3, GELU, 1x1] with the block's residual, and the value third
 // of CMTAttention.qkv_dwconv under the folded project_out.  As two launches (dwconv3x3_kernel, conv2d_mfma_kernel<1, 4, 1>) a
 // position moves 640 B: the 32-channel plane between them is written once and read once.  Here it never exists: 384 B.
 //
-// Bit-identical to the pair.  Every element takes the pair's path: dw_taps9's chain (bias, then the taps row by row, zero
-// padding as zero operands - formed one kernel row at a time with dw_taps3, as lfss_in_conv_mfma_kernel does), gelu_erf,
-// cv_split<false>, then per 16-channel chunk the three products (A_hi, B_hi), (A_hi, B_lo), (A_lo, B_hi) onto a zero
-// accumulator, then + bias, then + residual.
+// Bit-identical to the pair.  Every element takes the pair's path: dw_taps9's chain (dw_chain_step), gelu_erf, cv_split<false>,
+// then per 16-channel chunk the three products (cv_mma3) onto a zero accumulator, then + bias, then + residual.
 //
-// One wave walks a 32-column strip down a band of `rows` output rows.  Lane (pixel = lane & 31, k-half = lane >> 5) is the B-operand
-// lane of v_mfma_f32_32x32x16_bf16 for its pixel and holds, of both chunks, the 8 channels 16 cc + 8 (lane >> 5) + j: it forms
-// the depth-wise values of exactly those 16 channels, so the B fragments are built in registers - no staging through LDS.  An input
-// row is one 128-byte load per channel and half-wave; left / right neighbours come from the adjacent lanes (DPP), except in a
-// half's first / last lane (their DPP neighbour is the other half's pixel 31 / 0, another channel): those take the strip's outer
-// columns from one more load per channel, as lfss_out_conv_acc_kernel does.  Vertically a row is met once: it closes the chain
-// of output row r - 1, continues that of row r and opens that of row r + 1 (two partial sums per channel live across rows; a
-// band re-reads two rows of its neighbours, from cache).  LDS holds only constants: the taps, the prepared 1x1 weights and the bias.
+// Particular to this kernel: the depth-wise input is LOADED, so a strip is 32 whole columns with no halo lanes.  Lane (pixel =
+// lane & 31, k-half = lane >> 5) is the B-operand lane of v_mfma_f32_32x32x16_bf16 for its pixel and holds, of both chunks, the 8
+// channels 16 cc + 8 (lane >> 5) + j: it forms the depth-wise values of exactly those 16 channels, so the B fragments are built in
+// registers - no staging through LDS.  An input row is one 128-byte load per channel and half-wave; in a half's first / last lane
+// the DPP neighbour is the other half's pixel 31 / 0, another channel: those take the strip's outer columns from one more load per
+// channel, as lfss_out_conv_acc_kernel does.  A band re-reads two rows of its neighbours, from cache.  LDS holds only constants:
+// the taps, the prepared 1x1 weights and the bias.
 #pragma once
 #include <type_traits>
 #include "conv2d.hip.h"
-#include "dwconv.hip.h"
+#include "row_walk.hip.h"
 
 namespace wm {
 
@@ -39,14 +37,6 @@ struct DwPwArgs {
     long long nwalks;                 // B * nbands * nstrips (strips fastest)
 };
 
-// element at BYTE offset `boff` of a wave-uniform base
-__device__ __forceinline__ const float* dwpw_at(const float* base, unsigned boff) {
-    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + boff);
-}
-__device__ __forceinline__ float* dwpw_at(float* base, unsigned boff) {
-    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + boff);
-}
-
 #ifndef WM_DWPW_WAVES
 #define WM_DWPW_WAVES 3                // waves per SIMD the register allocation aims at
 #endif
@@ -59,52 +49,37 @@ __global__ __launch_bounds__(256, WM_DWPW_WAVES) void dw_pw_kernel(const DwPwArg
     __shared__ __attribute__((aligned(16))) float s_bias[C];          // 1x1 bias in accumulator order: [lane >> 5][register]
     const int lane = threadIdx.x & 63, px = lane & 31, kh = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // workgroup q runs on XCD q mod 8 (each with a private L2): every XCD gets a contiguous run of walks, so the two rows a band
-    // shares with the next come from the L2 that a neighbouring workgroup of the same XCD filled (the grid is a multiple of 8)
-    const long long blk = (long long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const bool live = blk * 4 + wv < a.nwalks;                        // (a wave past the last walk: the last walk's addresses, no stores)
-    const long long wk = live ? blk * 4 + wv : a.nwalks - 1;         // walk = (batch, band, strip), strips fastest
-    const int strip = (int)(wk % a.nstrips);
-    const long long wb = wk / a.nstrips;
-    const int band = (int)(wb % a.nbands);
-    const long long b = wb / a.nbands;
+    const RowWalk wk = row_walk(a.nwalks, a.nstrips, a.nbands, wv);
     const int H = a.H, W = a.W, HW = H * W;
-    const float* __restrict__ xb = a.x + b * a.xbs;
-    const float* __restrict__ rb = RES ? a.res + b * C * HW : nullptr;
-    float* __restrict__ yb = a.y + b * C * HW;
+    const float* __restrict__ xb = a.x + wk.b * a.xbs;
+    const float* __restrict__ rb = RES ? a.res + wk.b * C * HW : nullptr;
+    float* __restrict__ yb = a.y + wk.b * C * HW;
 
     // the lane's column, and the outer column of its side of the strip (clamped: loads are unconditional, masked when consumed)
-    const int col = strip * kCvTW + px;
+    const int col = wk.strip * kCvTW + px;
     const bool colok = col < W;
-    const int hcol = strip * kCvTW + (px < 16 ? -1 : kCvTW);
+    const int hcol = wk.strip * kCvTW + (px < 16 ? -1 : kCvTW);
     const bool hok = hcol >= 0 && hcol < W;
-    // Every access is a wave-uniform plane base (scalar registers) plus an unsigned 32-bit BYTE offset per lane - the one form
-    // that needs no 64-bit address arithmetic per load (9 H W floats at the most: H W < 2^26 keeps it below 2^32).
+    // byte offsets per lane: 9 H W floats at the most, H W < 2^26 keeps them below 2^32
     const unsigned xoff = 4u * (8 * kh * HW + min(col, W - 1)), xhoff = 4u * (8 * kh * HW + min(max(hcol, 0), W - 1));
     const unsigned ooff = 4u * (4 * kh * HW + min(col, W - 1));        // D layout: row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 
-    const int h0 = band * a.rows, hend = min(H, h0 + a.rows);
+    const int h0 = wk.band * a.rows, hend = min(H, h0 + a.rows);
     float cur[16], ecur[16];                                           // channel 16 cc + 8 kh + j at [8 cc + j]: centre, outer column
     {   // the band's first input row is on its way while the workgroup stages its constants
         const unsigned ro = 4u * (min(max(h0 - 1, 0), H - 1) * W);
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
             const float* __restrict__ pl = xb + (16 * (c >> 3) + (c & 7)) * HW;
-            cur[c] = *dwpw_at(pl, xoff + ro);
-            ecur[c] = *dwpw_at(pl, xhoff + ro);
+            cur[c] = *at_bytes(pl, xoff + ro);
+            ecur[c] = *at_bytes(pl, xhoff + ro);
         }
     }
-    if (threadIdx.x < C) {
-        const int i = threadIdx.x & 15;
-        s_bias[threadIdx.x] = a.bias ? a.bias[4 * (threadIdx.x >> 4) + (i & 3) + 8 * (i >> 2)] : 0.0f;
-    }
-    for (int i = threadIdx.x; i < C * 12; i += 256) {
-        const int c = i / 12, t = i - c * 12;
-        s_tap[i] = t < 9 ? a.dw_w[c * 9 + t] : (t == 9 && a.dw_b) ? a.dw_b[c] : 0.0f;
-    }
+    cv_stage_acc_bias<1>(s_bias, a.bias);
+    stage_dw_taps<C>(s_tap, a.dw_w, a.dw_b);
     s_A[threadIdx.x] = a.wfrag[threadIdx.x];
     __syncthreads();
-    if (!live) return;
+    if (!wk.live) return;
 
     float p0[16], p1[16];                                              // chains of output rows r + 1 and r after input row r
 #pragma unroll
@@ -119,9 +94,8 @@ __global__ __launch_bounds__(256, WM_DWPW_WAVES) void dw_pw_kernel(const DwPwArg
         const bool rowok = r >= 0 && r < H;                            // uniform
         const bool ok = rowok && colok, eok = rowok && hok;
         Frag16 Bh[2], Bl[2];
-        // the lane's 160 taps are read from LDS at every row: hoisted out of the row loop (the compiler's choice for loop-invariant
-        // reads) they fill the register file and spill.  An opaque per-lane OFFSET keeps them in the loop; the pointer stays an
-        // LDS pointer and the channel offsets land in the instructions' offset fields.
+        // the lane's 160 taps stay in the loop behind an opaque per-lane OFFSET: the pointer stays an LDS pointer and the channel
+        // offsets land in the instructions' offset fields
         int toff = 8 * kh * 12;
         asm volatile("" : "+v"(toff));
         const float* tap = s_tap + toff;
@@ -129,33 +103,26 @@ __global__ __launch_bounds__(256, WM_DWPW_WAVES) void dw_pw_kernel(const DwPwArg
         for (int c = 0; c < 16; ++c) {
             if constexpr (EMIT && RES) if (c == 8) {                                // the row's residual: half a row of arithmetic ahead of its use
 #pragma unroll
-                for (int i = 0; i < 16; ++i) rv[i] = *dwpw_at(rb + ((i & 3) + 8 * (i >> 2)) * HW, ooff + oro);
+                for (int i = 0; i < 16; ++i) rv[i] = *at_bytes(rb + (cv_acc_row(i)) * HW, ooff + oro);
             }
-            const float4* t4 = reinterpret_cast<const float4*>(tap + (16 * (c >> 3) + (c & 7)) * 12);
-            const float4 ta = t4[0], tb = t4[1], tc = t4[2];
-            const float t[10] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w, tc.x, tc.y};
+            float t[10];
+            load_dw_taps(tap, 16 * (c >> 3) + (c & 7), t);
             const float cv = ok ? cur[c] : 0.0f, ev = eok ? ecur[c] : 0.0f;
             const float* __restrict__ pl = xb + (16 * (c >> 3) + (c & 7)) * HW;      // wave-uniform plane base
-            cur[c] = *dwpw_at(pl, xoff + ron);
-            ecur[c] = *dwpw_at(pl, xhoff + ron);
+            cur[c] = *at_bytes(pl, xoff + ron);
+            ecur[c] = *at_bytes(pl, xhoff + ron);
             float left = dpp_from_lower_lane(cv, cv), right = dpp_from_upper_lane(cv, cv);
             if (px == 0) left = ev;
             if (px == kCvTW - 1) right = ev;
             const float row[3] = {left, cv, right};
-            float v = dw_taps3(p1[c], t + 6, row);
-            p1[c] = dw_taps3(p0[c], t + 3, row);
-            p0[c] = dw_taps3(t[9], t, row);
-            // (pinned here: the two chains are read in the next row only, and the optimiser otherwise sinks them - with this channel's
-            // taps and neighbours kept alive for them - below the row's stores)
-            asm volatile("" : "+v"(p0[c]), "+v"(p1[c]));
+            float v = dw_chain_step(p0[c], p1[c], t, row);
+            asm volatile("" : "+v"(p0[c]), "+v"(p1[c]));               // (pinned where they are formed)
             if constexpr (EMIT) {
                 if constexpr (GELU) v = gelu_erf(v);
                 asm("" : "+v"(v));                                     // the value the pair stored: the split below starts from these bits
                 cv_split<false>(v, Bh[c >> 3], Bl[c >> 3], c & 7);
             }
-            // left alone the scheduler interleaves all 16 channels (their taps, neighbours and products are independent) and the
-            // allocator then spills: one channel's temporaries at a time
-            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);                         // one channel's temporaries at a time
         }
         if constexpr (EMIT) {
             f32x16_t acc;
@@ -166,9 +133,7 @@ __global__ __launch_bounds__(256, WM_DWPW_WAVES) void dw_pw_kernel(const DwPwArg
                 Frag16 Ah, Al;
                 Ah.u = s_A[(cc * 2 + 0) * 64 + lane];
                 Al.u = s_A[(cc * 2 + 1) * 64 + lane];
-                acc = cv_mfma<false>(Ah, Bh[cc], acc);
-                acc = cv_mfma<false>(Ah, Bl[cc], acc);
-                acc = cv_mfma<false>(Al, Bh[cc], acc);
+                acc = cv_mma3(Ah, Al, Bh[cc], Bl[cc], acc);
             }
             const float4* b4 = reinterpret_cast<const float4*>(s_bias + 16 * kh);
 #pragma unroll
@@ -180,7 +145,7 @@ __global__ __launch_bounds__(256, WM_DWPW_WAVES) void dw_pw_kernel(const DwPwArg
                     const int i = 4 * q + j;
                     float v = acc[i] + bv[j];
                     if constexpr (RES) v += rv[i];
-                    if (colok) *dwpw_at(yb + ((i & 3) + 8 * (i >> 2)) * HW, ooff + oro) = v;
+                    if (colok) *at_bytes(yb + (cv_acc_row(i)) * HW, ooff + oro) = v;
                 }
             }
         }

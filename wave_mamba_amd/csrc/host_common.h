@@ -80,6 +80,30 @@ WM_HIDDEN int lds_optin(const void* fn, int bytes, bool (&flags)[64]);
 // compute units of the current device (asked once per device); returns WM_OK or WM_EHIP
 WM_HIDDEN int device_cus(int* ncu);
 
+// Launch geometry of the row-walking kernels (row_walk.hip.h): strips of `cols` output columns x bands of `rows` output rows, a walk
+// per (batch, band, strip), `wpw` walks per workgroup; xcd_runs: the kernel deals its workgroups to the 8 XCDs in contiguous runs
+// (row_walk), so the grid is rounded up to a multiple of 8.
+struct RowWalkGeom { int nstrips, nbands, rows; long long nwalks, nblocks; };
+static inline RowWalkGeom row_walk_geom(int B, int H, int W, int cols, int rows, int wpw, bool xcd_runs) {
+    RowWalkGeom g;
+    g.nstrips = (W + cols - 1) / cols; g.nbands = (H + rows - 1) / rows; g.rows = rows;
+    g.nwalks = (long long)B * g.nbands * g.nstrips;
+    g.nblocks = (g.nwalks + wpw - 1) / wpw;
+    if (xcd_runs) g.nblocks = (g.nblocks + 7) / 8 * 8;
+    return g;
+}
+// Rows per band of a kernel that RECOMPUTES its halo at two waves per SIMD: the chip holds 512 workgroups at a time and a launch
+// lasts about rounds x (rows + 2 recomputed + one of prologue) - of lo, lo + step, .. <= hi the first with the smallest product.
+static inline int row_walk_band_rows(int B, int H, int W, int cols, int wpw, int lo, int hi, int step) {
+    int rows = lo;
+    long long best = -1;
+    for (int cand = lo; cand <= hi; cand += step) {
+        const long long cost = ((row_walk_geom(B, H, W, cols, cand, wpw, false).nblocks + 511) / 512) * (cand + 3);
+        if (best < 0 || cost < best) { best = cost; rows = cand; }
+    }
+    return rows;
+}
+
 }  // namespace wm
 
 // Plane-dtype dispatch: runs CALL once with TP = float (plane_dtype == WM_F32) or TP = bf16_t (otherwise; callers have checked

@@ -162,6 +162,12 @@ static bool lfss_in_conv_domain(int H, int W, int C, int plane_dtype) {
     return C == 32 && plane_dtype == WM_F32 && W % 32 == 0 && (long long)H * W <= (1ll << 23);
 }
 
+// rows per band: a workgroup is two walks x two channel halves; the even height in [8, 64] of least cost (UHD level 1: 34 rows, 32
+// bands, 496 workgroups - one round).  Small maps get kInConvMinBand.
+static int lfss_in_conv_band_rows(int B, int H, int W) {
+    return row_walk_band_rows(B, H, W, kInConvCols, 2, kInConvMinBand, kInConvMaxBand, 2);
+}
+
 int wm_lfss_in_conv_band_rows(int B, int H, int W) {
     if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
     if (!lfss_in_conv_domain(H, W, 32, WM_F32)) return WM_EUNSUPPORTED;
@@ -176,17 +182,16 @@ int wm_lfss_in_conv_fwd(const float* tok, int tok_nchw, const float* ln_w, const
     if (B == 0 || H == 0 || W == 0) return WM_OK;
     if (!tok || !ln_w || !ln_b || !in_proj_weight || !conv_weight || !xc) return WM_ENULL;
     if (!tok_nchw && !aligned16(tok)) return WM_EALIGN;
-    const int nstrips = (W + kInConvCols - 1) / kInConvCols, rb = lfss_in_conv_band_rows(B, H, W), nbands = (H + rb - 1) / rb;
-    const long long nwalks = (long long)B * nbands * nstrips;
-    const dim3 grid((unsigned)((nwalks + 1) / 2));
+    const RowWalkGeom g = row_walk_geom(B, H, W, kInConvCols, lfss_in_conv_band_rows(B, H, W), 2, false);
+    const dim3 grid((unsigned)g.nblocks);
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(5, st);
     if (tok_nchw)
         hipLaunchKernelGGL(lfss_in_conv_mfma_kernel<true>, grid, dim3(256), 0, st, tok, ln_w, ln_b, ln_eps, in_proj_weight, conv_weight,
-                           conv_bias, xc, B, H, W, nstrips, nbands, rb, nwalks);
+                           conv_bias, xc, B, H, W, g.nstrips, g.nbands, g.rows, g.nwalks);
     else
         hipLaunchKernelGGL(lfss_in_conv_mfma_kernel<false>, grid, dim3(256), 0, st, tok, ln_w, ln_b, ln_eps, in_proj_weight, conv_weight,
-                           conv_bias, xc, B, H, W, nstrips, nbands, rb, nwalks);
+                           conv_bias, xc, B, H, W, g.nstrips, g.nbands, g.rows, g.nwalks);
     return launch_status();
 }
 
@@ -257,6 +262,11 @@ static bool lfss_ffn_domain(int H, int W, int C, int plane_dtype) {
     return C == 32 && plane_dtype == WM_F32 && W % 32 == 0 && (long long)H * W <= (1ll << 23);
 }
 
+// rows per band: four walks per workgroup; the height in [4, 64] of least cost (UHD level 1: 34 rows, 2048 walks - one round)
+static int lfss_ffn_band_rows(int B, int H, int W) {
+    return row_walk_band_rows(B, H, W, kFfnCols, 4, kFfnMinBand, kFfnMaxBand, 1);
+}
+
 int wm_lfss_ffn_band_rows(int B, int H, int W) {
     if (B < 0 || H < 0 || W < 0) return WM_EINVAL;
     if (!lfss_ffn_domain(H, W, 32, WM_F32)) return WM_EUNSUPPORTED;
@@ -273,17 +283,16 @@ int wm_lfss_ffn_fwd(const float* tok1, const float* ln2_w, const float* ln2_b, f
     if (!tok1 || !ln2_w || !ln2_b || !conv1_weight || !conv1_bias || !conv2_weight || !conv3_weight || !conv3_bias || !skip_scale2 || !out)
         return WM_ENULL;
     if (!aligned16(tok1) || (!out_nchw && !aligned16(out))) return WM_EALIGN;
-    const int nstrips = (W + kFfnCols - 1) / kFfnCols, rb = band_rows ? band_rows : lfss_ffn_band_rows(B, H, W), nbands = (H + rb - 1) / rb;
-    const long long nwalks = (long long)B * nbands * nstrips;
-    const dim3 grid((unsigned)((nwalks + 31) / 32 * 8));         // four walks per workgroup, a multiple of 8 workgroups (XCD runs)
+    const RowWalkGeom g = row_walk_geom(B, H, W, kFfnCols, band_rows ? band_rows : lfss_ffn_band_rows(B, H, W), 4, true);
+    const dim3 grid((unsigned)g.nblocks);
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(11, st);
     if (out_nchw)
         hipLaunchKernelGGL(lfss_ffn_mfma_kernel<true>, grid, dim3(256), 0, st, tok1, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
-                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, nstrips, nbands, rb, nwalks);
+                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, g.nstrips, g.nbands, g.rows, g.nwalks);
     else
         hipLaunchKernelGGL(lfss_ffn_mfma_kernel<false>, grid, dim3(256), 0, st, tok1, ln2_w, ln2_b, ln2_eps, conv1_weight, conv1_bias,
-                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, nstrips, nbands, rb, nwalks);
+                           conv2_weight, conv2_bias, conv3_weight, conv3_bias, skip_scale2, out, B, H, W, g.nstrips, g.nbands, g.rows, g.nwalks);
     return launch_status();
 }
 

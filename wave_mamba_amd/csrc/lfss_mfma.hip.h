@@ -24,19 +24,20 @@
 //   tile_normalise, xhalf_sum          LayerNorm statistics over a tile's 16 + 16 registers
 //   acc_quads / acc_rows, skip_add     accumulator registers from an LDS row; tok = tok * skip + acc
 //   aop_slot, acc_chan                 where A operand j of lane l sits in LDS; which channel K-step j carries
-//   stage_aop, stage_aop_blocks, stage_aop_rows, stage_W3, folded_bias, stage_dw_taps     weights into LDS before the group loop
+//   stage_aop, stage_aop_blocks, stage_aop_rows, stage_W3, folded_bias     weights into LDS before the group loop
 //   mfma_k4 / mfma_rows                THE K loop: one ds_read_b128 of A operands, then their MFMAs over the tiles.  Every
 //                                      projection runs through it, so lfss_out's K order (acc_chan) is the same in
 //                                      lfss_out_mfma, lfss_out_conv_mfma and lfss_out_conv_acc by construction
 //   store_rows64                       two tiles of a row block -> 256-byte runs of a plane
-//   plane_rsrc, buf_ld, load_dw_taps             memory / one channel plane as a raw buffer (raw_rsrc: dwconv.hip.h); a channel's taps from LDS
-//   dw_taps9, dw_taps3 (dwconv.hip.h)  the depth-wise sum in the depth-wise kernel's own order; one kernel row of it (lfss_in_conv
-//                                      continues three output rows' chains with each x row)
-//   lfss_in_conv_band_rows, lfss_ffn_band_rows   rows per band of lfss_in_conv / lfss_ffn (host)
+//   plane_rsrc, buf_ld                 memory / one channel plane as a raw buffer (raw_rsrc: dwconv.hip.h)
+//   dw_taps9 (dwconv.hip.h)            the depth-wise sum in the depth-wise kernel's own order
+//   stage_dw_taps, load_dw_taps, dw_chain_step, row_walk, HaloStrip (row_walk.hip.h)     the depth-wise tap table in LDS, and what
+//                                      the two row-walking kernels (lfss_in_conv, lfss_ffn) share with dw_pw_kernel and pw_dw_kernel
 #pragma once
 #include <hip/hip_runtime.h>
 #include "haar.hip.h"          // bf16_t, ld1 / st1 (fp32 and bf16 overloads)
 #include "dwconv.hip.h"        // dw_taps9, gelu_erf, dpp_from_lower_lane / dpp_from_upper_lane, raw_rsrc
+#include "row_walk.hip.h"
 
 // ---- tuning switches (tools/build_variant.sh and tools/bench_lfss_rz.py pass them with -D) --------------------------
 // waves per SIMD the middle kernel is compiled for.  Four (128 registers) spilled 46 vector registers of the ny = 4 fp32
@@ -188,19 +189,6 @@ __device__ __forceinline__ float folded_bias(const float* __restrict__ W, int ro
     float acc = start;
     for (int k = 0; k < 32; ++k) acc = fmaf(W[row * 32 + k], ln_b[k], acc);
     return acc;
-}
-// the depth-wise taps of 64 channels as [channel][9 taps | bias | 0 0]: three ds_read_b128 per channel (load_dw_taps)
-__device__ __forceinline__ void stage_dw_taps(float* s_cw, const float* __restrict__ cw /*(64, 3, 3)*/, const float* __restrict__ cbias) {
-    for (int e = threadIdx.x; e < 64 * 12; e += 256) {
-        const int c = e / 12, q = e - 12 * c;
-        s_cw[e] = q < 9 ? cw[c * 9 + q] : (q == 9 && cbias ? cbias[c] : 0.0f);
-    }
-}
-__device__ __forceinline__ void load_dw_taps(const float* s_cw, int c, float (&w)[10] /* 9 taps, bias */) {
-    const float* wk = s_cw + c * 12;
-    const float4 w0 = *reinterpret_cast<const float4*>(wk), w1 = *reinterpret_cast<const float4*>(wk + 4),
-                 w2 = *reinterpret_cast<const float4*>(wk + 8);
-    w[0] = w0.x; w[1] = w0.y; w[2] = w0.z; w[3] = w0.w; w[4] = w1.x; w[5] = w1.y; w[6] = w1.z; w[7] = w1.w; w[8] = w2.x; w[9] = w2.y;
 }
 
 // THE K loop.  mfma_k4: one ds_read_b128 of A operands 4 q .. 4 q + 3 of an LDS block in fetch order - K-steps j0 .. j0 + 3 - then
@@ -473,20 +461,14 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
 // ---- lfss_in_conv: tok -> xc = silu(dwconv3x3(x) + bias) (B, D, H, W); x never reaches memory ---------------------------
 // SS2D's prologue in one kernel (reference :483-487 behind ln_1: in_proj, chunk, NHWC -> NCHW, depth-wise 3x3, SiLU).  lfss_in wrote
 // x = in_proj(ln_1(tok))[:D] and dwconv3x3 read it back: 512 of the pair's 896 B per position.  The convolution needs x on a one-pixel
-// halo and x is a projection OUTPUT, so the halo is RECOMPUTED by the same matrix instructions:
-//   * a wave owns a strip of kInConvCols = 62 output columns - its 64 lanes are 64 consecutive image columns, one halo column each
-//     side - x a band of `rb` output rows (lfss_in_conv_band_rows) x 32 of the 64 channels (wave & 1), and walks the band's rb + 2 x
-//     rows top to bottom;
+// halo and x is a projection OUTPUT, so the halo is RECOMPUTED by the same matrix instructions.  The first of the row-walking kernels
+// (row_walk.hip.h: the scheme, what it costs to keep, the shared pieces); particular to it:
+//   * a strip is kInConvCols = 62 output columns on all 64 lanes (two pixel tiles, lanes 0 and 63 the halo columns), and a walk is split over two waves: each takes 32 of
+//     the 64 channels (wave & 1) of the band of `rb` output rows (lfss_in_conv_band_rows, lfss.hip);
 //   * per x row: the 64 columns' tokens (load_tile32) -> tile_normalise -> the x rows of in_proj through mfma_rows with lfss_in's A
-//     operands, K order and bias start (identical x bits) -> permlane32_swap: 32 registers, lane = column;
-//   * the taps: the horizontal neighbours are the adjacent LANES (DPP wave shifts), the vertical direction is THREE running chains
-//     per channel: x row r ends output row r - 1 with kernel row 2 (SiLU, store), continues output row r with kernel row 1 and
-//     starts output row r + 1 from the bias with kernel row 0 (dw_taps3) - each output is dw_taps9's one fmaf chain, so `xc` is
-//     BIT-IDENTICAL to the pair's on fp32 planes.  Zero padding (rows and columns outside the image) enters the chains as zero
-//     operands, selected where the x row is consumed.
-// The row loop has no lane-divergent branch and no branch at all around memory operations: token loads come from clamped addresses,
-// stores are raw buffer stores whose offset is out of range for a halo lane, a column past the image or a row outside the band; the
-// token rows are loaded TWO x rows ahead (two register buffers, the loop unrolled by two), issued before the row's 32 stores.
+//     operands, K order and bias start (identical x bits) -> permlane32_swap: 32 registers, lane = column; then dw_chain_step and
+//     SiLU, so `xc` is BIT-IDENTICAL to the pair's on fp32 planes;
+//   * the token rows are loaded TWO x rows ahead (two register buffers, the loop unrolled by two), issued before the row's 32 stores.
 // Columns: round 4's overlapping 62-column strips (248-byte store runs) are what is built; the aligned 64-column form with the two outer
 // columns from a third MFMA tile (+50 % matrix, LayerNorm and token-load work per row) was not built, so not measured: OPEN WORK - the
 // 248-byte misaligned store runs may be why the kernel moves its bytes at 2.7-2.9 TB/s and not at lfss_in's 3.8.
@@ -498,21 +480,7 @@ __global__ __launch_bounds__(256, WM_LFSS_IN_WAVES) void lfss_in_mfma_kernel(
 //   UHD level 2 ( 544 x  960, 10-row bands)  0.119 -> 0.091 ms / 0.126 -> 0.088 ms
 //   UHD level 3 ( 272 x  480,  8-row bands)  0.037 -> 0.049 ms / 0.038 -> 0.048 ms: slower - the operator layer keeps the pair there
 constexpr int kInConvCols = 62;                             // output columns per strip
-constexpr int kInConvMinBand = 8, kInConvMaxBand = 64;      // output rows per band (two more x rows are recomputed per band)
-// rows per band.  A workgroup is two strips x two channel halves at two waves per SIMD, so the chip holds 512 workgroups at a time and
-// a launch lasts about rounds x (rb + 2 x rows + one of prologue): the even rb in [8, 64] with the smallest such product (UHD level 1:
-// 34 rows, 32 bands, 496 workgroups - one round).  Small maps get kInConvMinBand.
-inline int lfss_in_conv_band_rows(int B, int H, int W) {
-    const long long nstrips = (W + kInConvCols - 1) / kInConvCols;
-    int rb = kInConvMinBand;
-    long long best = -1;
-    for (int cand = kInConvMinBand; cand <= kInConvMaxBand; cand += 2) {
-        const long long nb = (H + cand - 1) / cand, wgs = ((long long)B * nstrips * nb + 1) / 2;
-        const long long cost = ((wgs + 511) / 512) * (cand + 3);
-        if (best < 0 || cost < best) { best = cost; rb = cand; }
-    }
-    return rb;
-}
+constexpr int kInConvMinBand = 8, kInConvMaxBand = 64;      // output rows per band, even (two more x rows are recomputed per band)
 
 template <bool NCHW>
 __global__ __launch_bounds__(256, 2) void lfss_in_conv_mfma_kernel(
@@ -527,9 +495,11 @@ __global__ __launch_bounds__(256, 2) void lfss_in_conv_mfma_kernel(
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x < D) s_bias[threadIdx.x] = folded_bias(W_in, threadIdx.x, ln_b, 0.0f);
     stage_aop_rows<2>(s_A, W_in, ln_w);
-    stage_dw_taps(s_cw, cw, cb);
+    stage_dw_taps<D>(s_cw, cw, cb);
     __syncthreads();
     const long long L = (long long)H * W;
+    // (not row_walk - two walks per workgroup x a channel half, no XCD deal, another division scheme - and not HaloStrip: through
+    // either this kernel's instruction text changes, through the struct inside the token-row form's row loop)
     const long long wk = (long long)blockIdx.x * 2 + (wv >> 1);  // walk = (batch, band, strip), strips fastest
     const int hb = wv & 1;                                       // channel half: x channels 32 hb .. 32 hb + 31
     if (wk >= nwalks) return;
@@ -586,9 +556,7 @@ __global__ __launch_bounds__(256, 2) void lfss_in_conv_mfma_kernel(
                 const float t3[3] = {dpp_from_lower_lane(0.0f, xm), xm, dpp_from_upper_lane(0.0f, xm)};
                 float w[10];
                 load_dw_taps(s_cw, 32 * hb + ch, w);
-                const float o = dw_taps3(P1[q], w + 6, t3);
-                P1[q] = dw_taps3(P0[q], w + 3, t3);
-                P0[q] = dw_taps3(w[9], w, t3);
+                const float o = dw_chain_step(P0[q], P1[q], w, t3);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(silu_f(o)), rs, voff, ch * plane_bytes, 0);
             }
             __builtin_amdgcn_sched_barrier(0);                   // two channels' taps in registers at a time (all 32 hoisted: 380 spilled)
@@ -755,7 +723,7 @@ __global__ __launch_bounds__(256, 4) void lfss_out_conv_mfma_kernel(
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
     stage_W3(s_A3, W3);                                              // lfss_out's K order: bit-identical sums
-    stage_dw_taps(s_cw, cw, cbias);
+    stage_dw_taps<D>(s_cw, cw, cbias);
     __syncthreads();
     const long long g0 = (long long)blockIdx.x * 4 * gpw + wv;     // the block's waves walk adjacent groups together
     for (int gi = 0; gi < gpw; ++gi) {
@@ -833,7 +801,7 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x < C) { s_b3[threadIdx.x] = b3[threadIdx.x]; s_skip[threadIdx.x] = skip2[threadIdx.x]; }
     stage_W3(s_A3, W3);
-    stage_dw_taps(s_cw, cw, cbias);
+    stage_dw_taps<D>(s_cw, cw, cbias);
     __syncthreads();
     const long long wk = (long long)blockIdx.x * 4 + wv;         // walk = (batch, chunk of bands, strip), strips fastest
     if (wk >= nwalks) return;
@@ -929,36 +897,21 @@ __global__ __launch_bounds__(256, 2) void lfss_out_conv_acc_kernel(
 // ---- lfss_ffn: tok1 -> tok2; f = conv1(ln_2(tok1)) never reaches memory ---------------------------------------------------------
 // The gated ffn in one kernel (reference :226-230 behind ln_2, and the block's second skip connection :526).  lfss_mid wrote f (256 B
 // per position) and lfss_out_conv read it back on a one-pixel halo (486 B by the counters); f is a pointwise function of tok1, which
-// lfss_out_conv reads anyway, so here the halo is RECOMPUTED (pw_dw_kernel's layout on the fp32 matrix cores):
-//   * a wave owns a strip of kFfnCols = 30 output columns - its 32 pixel lanes are 32 consecutive image columns, one halo column each
-//     side, h = lane >> 5 is the k-half - x a band of `rb` output rows (lfss_ffn_band_rows), and walks the band's rb + 2 rows of tok1;
+// lfss_out_conv reads anyway, so here the halo is RECOMPUTED: a row-walking kernel (row_walk.hip.h: the scheme, what it costs to keep,
+// the shared pieces) in pw_dw_kernel's layout on the fp32 matrix cores.  Particular to it:
+//   * a strip is HaloStrip<kFfnCols = 30> on one 32-pixel tile, h = lane >> 5 is the k-half; the band is `rb` output rows
+//     (lfss_ffn_band_rows, lfss.hip);
 //   * per row: load_tile32 -> tile_normalise -> both row blocks of conv1 through mfma_rows with lfss_mid's A operands, K order and bias
-//     start (identical f bits): register i of block mt in lane (n, h) is channel 32 mt + acc_chan(i, h) of the lane's OWN pixel;
-//   * the taps: horizontal neighbours are the adjacent lanes (DPP; what the first / last pixel lane of a half takes is another
-//     channel's - those lanes are the halo columns and store nothing), the vertical direction is three running chains per channel
-//     (dw_taps3, as lfss_in_conv): each fc value is dw_taps9's one fmaf chain, zero padding enters as zero operands;
+//     start (identical f bits): register i of block mt in lane (n, h) is channel 32 mt + acc_chan(i, h) of the lane's OWN pixel, so
+//     the horizontal taps are DPP moves (what the first / last pixel lane of a half takes is another channel's: the halo lanes);
 //   * the GLU pair (c, c + 32) is register i of block 0 and of block 1 in the same lane, and the 16 gated values are conv3's B
 //     operands of K-steps 0 .. 15 as they stand (stage_W3's order, lfss_out's): no LDS exchange, no swap, no barrier in the row loop;
 //   * skip_add with the row's tok1 tile, RELOADED a row later (a cache hit) rather than kept: the row's registers take the load two
 //     rows ahead.
 // Every element takes the pair's arithmetic path: tok2 is BIT-IDENTICAL to wm_lfss_mid_rz_fwd's f stage + wm_lfss_out_conv_fwd on fp32
-// planes.  No branch around a memory operation in the row loop: loads come from clamped addresses, stores are raw buffer stores whose
-// offset is out of range for the halo lanes, columns past the image and rows outside the band.
+// planes.
 constexpr int kFfnCols = 30;                                // output columns per strip
 constexpr int kFfnMinBand = 4, kFfnMaxBand = 64;            // output rows per band (two more rows are recomputed per band)
-// rows per band.  A workgroup is four strips at two waves per SIMD, so the chip holds 512 workgroups at a time and a launch lasts about
-// rounds x (rb + 2 rows + one of prologue): the rb with the smallest such product (UHD level 1: 34 rows, 2048 walks - one round).
-inline int lfss_ffn_band_rows(int B, int H, int W) {
-    const long long nstrips = (W + kFfnCols - 1) / kFfnCols;
-    int rb = kFfnMinBand;
-    long long best = -1;
-    for (int cand = kFfnMinBand; cand <= kFfnMaxBand; ++cand) {
-        const long long nb = (H + cand - 1) / cand, wgs = ((long long)B * nstrips * nb + 3) / 4;
-        const long long cost = ((wgs + 511) / 512) * (cand + 3);
-        if (best < 0 || cost < best) { best = cost; rb = cand; }
-    }
-    return rb;
-}
 
 typedef unsigned lfss_v4u __attribute__((ext_vector_type(4)));
 
@@ -977,19 +930,11 @@ __global__ __launch_bounds__(256, 2) void lfss_ffn_mfma_kernel(
     __shared__ __attribute__((aligned(16))) float s_cw[D * 12];                  // [channel][9 taps | bias | 0 0]
     const int lane = threadIdx.x & 63, n = lane & 31, h = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // workgroup q runs on XCD q mod 8 (each with a private L2): every XCD gets a contiguous run of walks (the grid is a multiple of 8)
-    const long long blk = (long long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const bool live = blk * 4 + wv < nwalks;                     // (a wave past the last walk: the last walk's addresses, no loop)
-    const long long wk = live ? blk * 4 + wv : nwalks - 1;       // walk = (batch, band, strip), strips fastest
-    const int strip = (int)(wk % nstrips);
-    const int band = (int)((wk / nstrips) % nbands);
-    const long long b = wk / ((long long)nstrips * nbands);
-    const long long L = (long long)H * W;
-    const int col = strip * kFfnCols - 1 + n;                    // the lane's image column (pixel lanes 0 and 31: the halo columns)
-    const int colc = min(max(col, 0), W - 1);
-    const bool colin = col >= 0 && col < W;
-    const bool st_ok = n >= 1 && n <= kFfnCols && col < W;
-    const int r0 = band * rb, r_end = min(H, r0 + rb);
+    const RowWalk wk = row_walk(nwalks, nstrips, nbands, wv);
+    const long long b = wk.b, L = (long long)H * W;
+    const HaloStrip<kFfnCols> hs(wk.strip, n, W);
+    const int colc = hs.colc(W);
+    const int r0 = wk.band * rb, r_end = min(H, r0 + rb);
     // the image's output as one raw buffer of 128 L bytes (L <= 2^23); an offset >= nrec is dropped
     const unsigned plane_bytes = (unsigned)(L * 4), nrec = 32u * plane_bytes;
     const __amdgpu_buffer_rsrc_t rs = raw_rsrc(out + b * C * L, (int)nrec);
@@ -1012,9 +957,9 @@ __global__ __launch_bounds__(256, 2) void lfss_ffn_mfma_kernel(
     }
     stage_aop_rows<2>(s_A1, W1, ln2_w);                          // lfss_mid's conv1 operands
     stage_W3(s_A3, W3);                                          // lfss_out's K order: bit-identical sums
-    stage_dw_taps(s_cw, cw, cbias);
+    stage_dw_taps<D>(s_cw, cw, cbias);
     __syncthreads();
-    if (!live) return;
+    if (!wk.live) return;
 
     // the chains of output rows r + 1 (P0: bias + kernel row 0 so far) and r (P1: + kernel row 1) after f row r, of channel
     // 32 mt + acc_chan(i, h) at [16 mt + i]
@@ -1041,9 +986,9 @@ __global__ __launch_bounds__(256, 2) void lfss_ffn_mfma_kernel(
             acc_rows(s_b1 + 32 * mt, ho, fa[mt][0]);
             mfma_rows<C / 8>(s_A1, 4 * mt, lo, [=](int j, int) { return a[j]; }, fa[mt]);
         }
-        const bool keep = colin && rho >= 0 && rho < H;          // else: zero padding
+        const bool keep = hs.colin && rho >= 0 && rho < H;       // else: zero padding
         const bool orow = rho - 1 >= r0 && rho - 1 < r_end;      // (wave-uniform)
-        const unsigned voff = (st_ok && orow) ? lane_off + (unsigned)(rho - 1) * row_bytes : nrec;
+        const unsigned voff = (hs.st_ok && orow) ? lane_off + (unsigned)(rho - 1) * row_bytes : nrec;
         float g[16];                                             // gelu(gate) * value of channel acc_chan(i, h): conv3's B operands
         // (two forms measured the same and were not kept: the next pair's taps read from LDS under this pair's chains - 36 more
         // registers; and a software pipeline with row rho + 1's conv1 and this row's conv3 K-steps issued between the pairs' chains - 254
@@ -1058,11 +1003,8 @@ __global__ __launch_bounds__(256, 2) void lfss_ffn_mfma_kernel(
                 const float t3[3] = {dpp_zero_from_lower_lane(xm), xm, dpp_zero_from_upper_lane(xm)};
                 float w[10];
                 load_dw_taps(s_cw, 32 * mt + acc_chan(i, ho), w);
-                fc[mt] = dw_taps3(P1[q], w + 6, t3);
-                P1[q] = dw_taps3(P0[q], w + 3, t3);
-                P0[q] = dw_taps3(w[9], w, t3);
-                // (pinned here: the two chains are read in the next row only, and the optimiser otherwise sinks them below the stores)
-                asm volatile("" : "+v"(P0[q]), "+v"(P1[q]));
+                fc[mt] = dw_chain_step(P0[q], P1[q], w, t3);
+                asm volatile("" : "+v"(P0[q]), "+v"(P1[q]));     // (pinned where they are formed)
             }
             g[i] = gelu_erf(fc[0]) * fc[1];
             asm volatile("" : "+v"(g[i]));                       // (formed here: left alone, erf's tail and the product sink to the MFMAs)

@@ -1,5 +1,6 @@
 // pw_dw.hip.h - LayerNorm2d, a 1x1 convolution and the depth-wise 3x3 (+ bias) that alone reads its first Cdw output channels, in one
-// kernel: the mirror image of dw_pw.hip.h, for gfx950.  x (B, 32, H, W) fp32, NCHW.
+// kernel: the mirror image of dw_pw.hip.h, for gfx950.  x (B, 32, H, W) fp32, NCHW.  One of the row-walking kernels: the scheme,
+// what it costs to keep and the shared pieces are in row_walk.hip.h.
 //   y[:, :Cdw] = dwconv3x3(conv1x1(LayerNorm2d(x)) + b_pw)[:, :Cdw] + b_dw
 //   y[:, Cdw:] = (conv1x1(LayerNorm2d(x)) + b_pw)[:, Cdw:]
 //
@@ -10,38 +11,21 @@
 //
 // Bit-identical to the pair; every element takes the pair's path.  LayerNorm: conv2d_mfma_kernel's LNIN block - the mean by plain adds
 // and the variance by an fmaf chain, both over the channels in order 0 .. 31, rstd = 1 / sqrtf(var / 32 + eps), then
-// fmaf((v - mean) rstd, w, b).  1x1: cv_split<false>, conv2d_prep_kernel's fragments, per 16-channel chunk the three products (A_hi,
-// B_hi), (A_hi, B_lo), (A_lo, B_hi) onto a zero accumulator, then + bias.  Depth-wise: dw_taps9's chain (bias, then the taps row by
-// row, zero padding - zero, not the 1x1 of a normalised zero pixel - as zero operands), formed one kernel row at a time with
-// dw_taps3 as lfss_in_conv_mfma_kernel and dw_pw_kernel form it.
+// fmaf((v - mean) rstd, w, b).  1x1: cv_split<false>, conv2d_prep_kernel's fragments, per 16-channel chunk the three products (cv_mma3)
+// onto a zero accumulator, then + bias.  Depth-wise: dw_taps9's chain (dw_chain_step); zero padding is zero, not the 1x1 of a
+// normalised zero pixel.
 //
-// One wave walks a strip of kPwDwCols = 30 output columns down a band of `rows` output rows.  Its 32 pixel lanes are 32 consecutive
-// image columns, one halo column each side: the depth-wise input is a 1x1 OUTPUT, so the halo is recomputed, not loaded (strips overlap
-// by one column each side, bands by one x row each side - lfss_in_conv's 62-of-64 choice on one pixel tile).  Lane (pixel = lane & 31,
-// k-half = lane >> 5) is the B-operand lane of v_mfma_f32_32x32x16_bf16 and loads, of both 16-channel chunks, the 8 channels
-// 16 cc + 8 (lane >> 5) + j of its pixel; the other 16 arrive from lane ^ 32 by v_permlane32_swap, and every lane runs the whole
-// 32-term chains.  After the six products of a 32-channel row tile the accumulator holds 16 output channels of the lane's OWN pixel:
-// the horizontal taps are DPP moves from the adjacent lanes (what the first / last pixel lane of a half takes is another channel's:
-// those two lanes are the halo columns and store nothing), the vertical direction is three running chains per channel - x row r
-// closes output row r - 1, continues row r and opens row r + 1; two partial sums per channel live across rows.  All NT row tiles run
-// in the one wave (LayerNorm once per pixel), so the q | k head carries 64 partial sums.
-//
-// What the sibling kernels paid for, as it applies here:
-//   * no branch around a memory operation in the row loop: loads come from clamped addresses and are masked where the row is consumed;
-//     stores are raw buffer stores whose offset is out of range for the halo lanes, columns past the image and rows outside the band;
-//   * addresses are wave-uniform plane bases plus an unsigned 32-bit BYTE offset per lane (H W < 2^25: a 32-plane output tile is one
-//     raw buffer of less than 2^32 bytes);
-//   * the taps, the 1x1 fragments, the bias and the LayerNorm weights are re-read from LDS per row behind an opaque offset (hoisted
-//     out of the row loop they spill);
-//   * the partial sums are pinned where they are formed;
-//   * an x row is loaded two rows ahead of its use (two register buffers, the loop unrolled by two), into the registers the row just
-//     normalised leaves free and ahead of the row's stores;
-//   * workgroup ids are dealt to the XCDs in contiguous runs, so that neighbouring strips and bands share an L2;
-//   * every address lies inside its tensor at every shape: clamped rows and columns for the loads, dropped stores otherwise.
+// Particular to this kernel: the depth-wise input is a 1x1 OUTPUT, so a strip is HaloStrip<kPwDwCols = 30> on one 32-pixel tile.
+// Lane (pixel = lane & 31, k-half = lane >> 5) is the B-operand lane of v_mfma_f32_32x32x16_bf16 and loads, of both 16-channel chunks,
+// the 8 channels 16 cc + 8 (lane >> 5) + j of its pixel; the other 16 arrive from lane ^ 32 by v_permlane32_swap, and every lane runs
+// the whole 32-term chains.  After the six products of a 32-channel row tile the accumulator holds 16 output channels of the lane's OWN
+// pixel, so the horizontal taps are DPP moves (what the first / last pixel lane of a half takes is another channel's: those are the
+// halo lanes).  All NT row tiles run in the one wave (LayerNorm once per pixel), so the q | k head carries 64 partial sums.  Beside the
+// taps, the 1x1 fragments, the bias and the LayerNorm weights are re-read from LDS per row; an x row is loaded two rows ahead of its use
+// (two register buffers, the loop unrolled by two).  H W < 2^25: a 32-plane output tile is one raw buffer of less than 2^32 bytes.
 #pragma once
 #include "conv2d.hip.h"
-#include "dwconv.hip.h"
-#include "dw_pw.hip.h"                 // dwpw_at
+#include "row_walk.hip.h"
 
 namespace wm {
 
@@ -73,35 +57,26 @@ __global__ __launch_bounds__(256, 2) void pw_dw_kernel(const PwDwArgs a) {
     __shared__ __attribute__((aligned(16))) float s_ln[2 * 2 * 16];      // [lane >> 5][weight | bias][8 cc + j] of channel 16 cc + 8 (lane >> 5) + j
     const int lane = threadIdx.x & 63, px = lane & 31, kh = lane >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // workgroup q runs on XCD q mod 8 (each with a private L2): every XCD gets a contiguous run of walks (the grid is a multiple of 8)
-    const long long blk = (long long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const bool live = blk * 4 + wv < a.nwalks;                          // (a wave past the last walk: the last walk's addresses, no loop)
-    const long long wk = live ? blk * 4 + wv : a.nwalks - 1;           // walk = (batch, band, strip), strips fastest
-    const int strip = (int)(wk % a.nstrips);
-    const long long wb = wk / a.nstrips;
-    const int band = (int)(wb % a.nbands);
-    const long long b = wb / a.nbands;
+    const RowWalk wk = row_walk(a.nwalks, a.nstrips, a.nbands, wv);
     const int H = a.H, W = a.W, HW = H * W;
-    const float* __restrict__ xb = a.x + b * C * HW;
-    float* __restrict__ yb = a.y + b * (NT * 32) * HW;
+    const float* __restrict__ xb = a.x + wk.b * C * HW;
+    float* __restrict__ yb = a.y + wk.b * (NT * 32) * HW;
 
-    const int col = strip * kPwDwCols - 1 + px;                         // the lane's image column (pixel lanes 0 and 31: the halo columns)
-    const bool colin = col >= 0 && col < W;
-    const bool st_ok = px >= 1 && px <= kPwDwCols && col < W;
-    const unsigned xoff = 4u * (8 * kh * HW + min(max(col, 0), W - 1));
+    const HaloStrip<kPwDwCols> hs(wk.strip, px, W);
+    const unsigned xoff = 4u * (8 * kh * HW + hs.colc(W));
     // a row tile's 32 output planes as one raw buffer; D layout: row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) - the lane's part of
     // it in the lane's offset, the register's in the scalar offset; an offset >= nrec is dropped
     const unsigned plane_bytes = 4u * HW, nrec = 32u * plane_bytes;
-    const unsigned lane_off = 4u * (4 * kh * HW + min(col, W - 1));
+    const unsigned lane_off = 4u * (4 * kh * HW + min(hs.col, W - 1));
     __amdgpu_buffer_rsrc_t rs[NT];
 #pragma unroll
     for (int m = 0; m < NT; ++m) rs[m] = raw_rsrc(yb + (long long)m * 32 * HW, (int)nrec);
 
-    const int r0 = band * a.rows, r_end = min(H, r0 + a.rows);
+    const int r0 = wk.band * a.rows, r_end = min(H, r0 + a.rows);
     auto load_row = [&](int rho, float (&nx)[16]) {                     // channel 16 cc + 8 kh + j at [8 cc + j]; clamped, masked when consumed
         const unsigned ro = 4u * (min(max(rho, 0), H - 1) * W);
 #pragma unroll
-        for (int c = 0; c < 16; ++c) nx[c] = *dwpw_at(xb + (16 * (c >> 3) + (c & 7)) * HW, xoff + ro);
+        for (int c = 0; c < 16; ++c) nx[c] = *at_bytes(xb + (16 * (c >> 3) + (c & 7)) * HW, xoff + ro);
     };
     float nxa[16], nxb[16];
     load_row(r0 - 1, nxa);                                              // on their way while the workgroup stages its constants
@@ -109,21 +84,15 @@ __global__ __launch_bounds__(256, 2) void pw_dw_kernel(const PwDwArgs a) {
     load_row(r0, nxb);
     __builtin_amdgcn_sched_barrier(0);
 
-    for (int i = threadIdx.x; i < NT * 32; i += 256) {
-        const int r = i & 15;
-        s_bias[i] = a.bias ? a.bias[32 * (i >> 5) + 4 * ((i >> 4) & 1) + (r & 3) + 8 * (r >> 2)] : 0.0f;
-    }
-    for (int i = threadIdx.x; i < NDW * 32 * 12; i += 256) {
-        const int c = i / 12, t = i - c * 12;
-        s_tap[i] = t < 9 ? a.dw_w[c * 9 + t] : (t == 9 && a.dw_b) ? a.dw_b[c] : 0.0f;
-    }
+    cv_stage_acc_bias<NT>(s_bias, a.bias);
+    stage_dw_taps<NDW * 32>(s_tap, a.dw_w, a.dw_b);
     if (threadIdx.x < 64) {
         const int h = threadIdx.x >> 5, e = threadIdx.x & 15, c = 16 * (e >> 3) + 8 * h + (e & 7);
         s_ln[threadIdx.x] = (threadIdx.x & 16) ? a.ln_b[c] : a.ln_w[c];
     }
     for (int i = threadIdx.x; i < 2 * NT * 2 * 64; i += 256) s_A[i] = a.wfrag[i];
     __syncthreads();
-    if (!live) return;
+    if (!wk.live) return;
 
     // the chains of output rows r + 1 (p0: bias + kernel row 0 so far) and r (p1: + kernel row 1) after x row r, of channel
     // 32 m + 4 kh + (i & 3) + 8 (i >> 2) at [16 m + i]
@@ -167,10 +136,10 @@ __global__ __launch_bounds__(256, 2) void pw_dw_kernel(const PwDwArgs a) {
         load_row(rho + 2, nx);                                          // two rows ahead, ahead of this row's stores
         __builtin_amdgcn_sched_barrier(0);
         const bool rowin = rho >= 0 && rho < H;                         // (wave-uniform)
-        const bool keep = colin && rowin;                               // else: zero padding
+        const bool keep = hs.colin && rowin;                               // else: zero padding
         const bool orow_dw = rho - 1 >= r0 && rho - 1 < r_end, orow_pw = rho >= r0 && rho < r_end;
-        const unsigned voff_dw = (st_ok && orow_dw) ? lane_off + 4u * ((rho - 1) * W) : nrec;
-        const unsigned voff_pw = (st_ok && orow_pw) ? lane_off + 4u * (rho * W) : nrec;
+        const unsigned voff_dw = (hs.st_ok && orow_dw) ? lane_off + 4u * ((rho - 1) * W) : nrec;
+        const unsigned voff_pw = (hs.st_ok && orow_pw) ? lane_off + 4u * (rho * W) : nrec;
 #pragma unroll
         for (int m = 0; m < NT; ++m) {
             f32x16_t acc;
@@ -181,9 +150,7 @@ __global__ __launch_bounds__(256, 2) void pw_dw_kernel(const PwDwArgs a) {
                 Frag16 Ah, Al;
                 Ah.u = s_A[((cc * NT + m) * 2 + 0) * 64 + lo];
                 Al.u = s_A[((cc * NT + m) * 2 + 1) * 64 + lo];
-                acc = cv_mfma<false>(Ah, Bh[cc], acc);
-                acc = cv_mfma<false>(Ah, Bl[cc], acc);
-                acc = cv_mfma<false>(Al, Bh[cc], acc);
+                acc = cv_mma3(Ah, Al, Bh[cc], Bl[cc], acc);
             }
             const float4* b4 = reinterpret_cast<const float4*>(s_bias + 32 * m + 16 * ko);
             const float* tap = s_tap + (32 * m + 4 * ko) * 12;
@@ -193,21 +160,17 @@ __global__ __launch_bounds__(256, 2) void pw_dw_kernel(const PwDwArgs a) {
                 const float bv[4] = {bq.x, bq.y, bq.z, bq.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int i = 4 * q + j, ch = (i & 3) + 8 * (i >> 2);
+                    const int i = 4 * q + j, ch = cv_acc_row(i);
                     float v = acc[i] + bv[j];
                     if (m < NDW) {
                         asm("" : "+v"(v));                             // the value the pair stored: the depth-wise chains start from these bits
                         const float xm = keep ? v : 0.0f;
                         const float t3[3] = {dpp_from_lower_lane(0.0f, xm), xm, dpp_from_upper_lane(0.0f, xm)};
-                        const float4* t4 = reinterpret_cast<const float4*>(tap + ch * 12);
-                        const float4 ta = t4[0], tb = t4[1], tc = t4[2];
-                        const float t[10] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w, tc.x, tc.y};
+                        float t[10];
+                        load_dw_taps(tap, ch, t);
                         const int pq = 16 * (m < NDW ? m : 0) + i;
-                        v = dw_taps3(p1[pq], t + 6, t3);
-                        p1[pq] = dw_taps3(p0[pq], t + 3, t3);
-                        p0[pq] = dw_taps3(t[9], t, t3);
-                        // (pinned here: the two chains are read in the next row only, and the optimiser otherwise sinks them below the stores)
-                        asm volatile("" : "+v"(p0[pq]), "+v"(p1[pq]));
+                        v = dw_chain_step(p0[pq], p1[pq], t, t3);
+                        asm volatile("" : "+v"(p0[pq]), "+v"(p1[pq]));   // (pinned where they are formed)
                     }
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs[m], (int)(m < NDW ? voff_dw : voff_pw),
                                                           (int)(ch * plane_bytes), 0);
