@@ -42,8 +42,8 @@ extern "C" {
 #define WM_F32 0
 #define WM_BF16 1
 
-/* ABI version of this header (bumped on any signature change; entry points that are only ADDED - the _det forms and the channel
- * gather - change no signature a caller compiled against 34 uses, so they do not bump it). */
+/* ABI version of this header (bumped on any signature change; entry points that are only ADDED - the _det forms, the channel
+ * gather and wm_grad_guard - change no signature a caller compiled against 34 uses, so they do not bump it). */
 int wm_abi_version(void);
 /* Identity of the sources this binary was compiled from: the first 16 hex digits of a sha256 over csrc/ and this header
  * (wave_mamba_amd/build.py passes it as -DWM_BUILD_ID; "unknown" for a bare hipcc build).  Measurements that describe
@@ -643,6 +643,32 @@ int wm_selscan_bwd_det(const float* u, const float* delta, const float* A, const
  * WM_ENULL; WM_EALIGN: a pointer not 4-byte aligned; WM_EUNSUPPORTED: B or the grid's channel axis > 65535, M > 1024 (backward). */
 int wm_channel_gather_fwd(const float* x, const int* index, float* y, int B, int C, int M, int64_t HW, void* stream);
 int wm_channel_gather_bwd(const float* gy, const int* index, float* gx, int B, int C, int M, int64_t HW, void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Guarded optimizer step (csrc/grad_guard.hip.h): the global L2 norm of a set of fp32 gradients, a non-finite flag and the clipping
+ * divisor, left on the device for the optimizer launch that follows on the same stream - torch's fused AdamW reads them as
+ * `found_inf` and `grad_scale` - so a step captured into a HIP graph can skip itself and clip without the host.  Reference
+ * counterpart: none (femasr_model.py:157-185 steps unconditionally); the divisor is torch.nn.utils.clip_grad_norm_'s coefficient,
+ * inverted.  (Added to ABI 34 like the _det forms: no existing signature changes.)
+ *   table    n_rows rows {int64 address, int64 count} in DEVICE memory: each a run of `count` >= 0 contiguous floats starting at
+ *            any 4-byte boundary.  The host splits a tensor into runs of at most 4096 floats (one workgroup per row; a longer run
+ *            is summed correctly, by one workgroup); a run never spans two tensors.
+ *   record   4 floats, OVERWRITTEN: {norm, found_inf, grad_scale, 0}
+ *              norm       = (float) sqrt(sum of squares), every square and every add in double (1e19 and 1e-30 both survive)
+ *              found_inf  = 1 if any element has all exponent bits set (inf, NaN - tested on the bit pattern) or norm is not
+ *                           finite in fp32 (finite elements can overflow it), else 0
+ *              grad_scale = max(1, (norm + 1e-6f) / max_norm) in fp32 when max_norm is finite and > 0 and found_inf == 0, else 1
+ *   skipped  one int64 (may be NULL): skipped[0] += found_inf, a plain read-modify-write by one thread
+ *   ws       wm_grad_guard_workspace_bytes(n_rows) bytes (16 per row; 0 for no rows), uninitialised: one {double, flag} per row is
+ *            written by its workgroup and read by the finishing workgroup, which adds the rows in an order fixed by n_rows.
+ * No atomics, no memset: bit-identical run to run, and nothing is assumed about what ws or record held.
+ * Status, by host arithmetic before any launch: WM_EINVAL n_rows < 0; WM_ENULL record; n_rows == 0 then writes {0, 0, 1, 0} (one
+ * launch); WM_ENULL table or ws; WM_EWORKSPACE; WM_EUNSUPPORTED n_rows >= 2^31; WM_EALIGN table, ws or skipped not 8-byte, record
+ * not 4-byte aligned.
+ * -------------------------------------------------------------------------------------------- */
+size_t wm_grad_guard_workspace_bytes(int64_t n_rows);
+int wm_grad_guard(const void* table, int64_t n_rows, float max_norm, float* record, int64_t* skipped, void* ws, size_t ws_bytes,
+                  void* stream);
 
 /* Host-blocking wait for `event` (a hipEvent_t recorded OUTSIDE any capture) that is legal while a stream of this
  * thread is being captured: hipEventSynchronize under a thread-local relaxed capture mode

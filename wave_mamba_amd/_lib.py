@@ -116,6 +116,8 @@ SIGNATURES = {
     "wm_selscan_bwd_det": (_i, [_p] * 15 + [_p, _sz] + [_i] * 6 + [_p]),
     "wm_channel_gather_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
     "wm_channel_gather_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
+    "wm_grad_guard_workspace_bytes": (_sz, [_i64]),
+    "wm_grad_guard": (_i, [_p, _i64, _c.c_float, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

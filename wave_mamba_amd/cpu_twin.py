@@ -7,6 +7,8 @@ LOLv1 / 1x3x256x256 "CPU-only PyTorch forward (plumbing, no GPU)").
     ss2d_core           SS2D.forward_core           :446-478 (for the torch.library op wavemamba_hip::ss2d_core on CPU tensors)
     paired_patches      the train phase of PairedImageDataset.__getitem__ after the decode + default collate
                         (/root/reference/basicsr/data/paired_image_dataset.py:80-131; host form of ops.paired_patches_u8)
+    grad_guard          gradient norm, non-finite flag and clipping divisor of the guarded optimizer step (no reference counterpart;
+                        host form of ops.grad_guard)
 
 Plain PyTorch, differentiable by autograd, written from the operators' definitions.  They are
 the implementation for CPU TENSORS and nothing else: `ops.py` selects them by the device of the input, never by the absence of
@@ -187,3 +189,23 @@ def paired_patches(pairs, rows, gt_size, swap_rb=True):
             out[k].append(a.permute(2, 0, 1).to(torch.float32) / 255.0)
     empty = torch.empty(0, 3, P, P, dtype=torch.float32)
     return tuple(torch.stack(o) if o else empty.clone() for o in out)
+
+
+def grad_guard(tensors, max_norm=None):
+    """The record of ops.grad_guard / wm_grad_guard in plain PyTorch: 4 float32 on the CPU, {norm, found_inf, grad_scale, 0}.
+    norm = float32(sqrt(sum of squares)) with every square and add in float64; found_inf = 1 when an element is not finite or the
+    norm is not finite in float32; grad_scale = max(1, (norm + 1e-6) / max_norm) in float32 arithmetic when max_norm is a finite
+    positive number and found_inf is 0, else 1 (torch.nn.utils.clip_grad_norm_'s coefficient, inverted).  The decision of the guarded
+    step for CPU tensors (trainer.GradGuard), and the yardstick of the kernel's tests."""
+    total = torch.zeros((), dtype=torch.float64)
+    finite = True
+    for t in tensors:
+        d = t.detach().to("cpu", torch.float64).reshape(-1)
+        finite = finite and bool(torch.isfinite(d).all())
+        total = total + (d * d).sum()
+    norm = total.sqrt().to(torch.float32)
+    found = not finite or not bool(torch.isfinite(norm))
+    scale = torch.ones((), dtype=torch.float32)
+    if max_norm is not None and 0.0 < float(max_norm) < float("inf") and not found:
+        scale = torch.clamp((norm + torch.tensor(1e-6, dtype=torch.float32)) / torch.tensor(float(max_norm), dtype=torch.float32), min=1.0)
+    return torch.stack([norm, torch.tensor(1.0 if found else 0.0), scale, torch.zeros(())])

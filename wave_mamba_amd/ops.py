@@ -1774,6 +1774,100 @@ def l1_mean(a, b):
     return _L1Mean.apply(a.contiguous().float(), b.contiguous().float())
 
 
+GRAD_GUARD_CHUNK = 4096                    # csrc/grad_guard.hip.h: kGuardChunk - floats per table row (one workgroup each)
+
+
+class _GuardTableUpload:
+    """The two pinned slots (an event each) behind grad_guard_table, per device: PairedPatchBatcher's discipline - the host rewrites
+    a slot only after the copy out of it has finished, so building the next step's table does not wait for this step's copy."""
+
+    def __init__(self):
+        self.pin, self.copied, self.slot = [None, None], [None, None], 0
+
+    def upload(self, rows, dev):
+        slot = self.slot
+        self.slot ^= 1
+        if self.copied[slot] is not None:
+            self.copied[slot].synchronize()                        # the last copy out of this pinned slot
+        pin = self.pin[slot]
+        if pin is None or pin.shape[0] < len(rows):
+            pin = self.pin[slot] = torch.empty((max(len(rows), 1024), 2), dtype=torch.int64, pin_memory=True)
+        pin.numpy()[:len(rows)] = rows
+        table = torch.empty((len(rows), 2), dtype=torch.int64, device=dev)
+        table.copy_(pin[:len(rows)], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        self.copied[slot] = ev
+        return table
+
+
+_GUARD_UPLOADS = {}          # device index -> _GuardTableUpload
+
+
+def grad_guard_table(tensors):
+    """The device table wm_grad_guard reads, for a list of contiguous float32 CUDA tensors (one device): rows {address, count} of at
+    most GRAD_GUARD_CHUNK floats, a tensor of more being split, an empty tensor giving no row; no row spans two tensors.
+    -> (table (n_rows, 2) int64 on the device, n_rows).  The upload is a pinned-to-device copy on the current stream, so the table is
+    always built OUTSIDE a graph capture (RuntimeError inside one); it holds raw addresses - the caller keeps the tensors alive and
+    in place for as long as the table is used (a captured step: one flat gradient buffer, allocated before the capture), and a
+    launch captured into a graph holds the address of the TABLE as well: keep the table for as long as the graph is replayed."""
+    tensors = list(tensors)
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            what = f"{t.dtype} on {t.device}, contiguous: {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"grad_guard_table: contiguous float32 CUDA tensors only, got {what}")
+    if len({t.device for t in tensors}) > 1:
+        raise ValueError("grad_guard_table: the tensors live on more than one device")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("grad_guard_table: a host-to-device copy must not be captured - build the table before the capture")
+    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    rows = []
+    for t in tensors:
+        base, n = t.data_ptr(), t.numel()
+        rows.extend((base + 4 * at, min(GRAD_GUARD_CHUNK, n - at)) for at in range(0, n, GRAD_GUARD_CHUNK))
+    if not rows:
+        return torch.empty((0, 2), dtype=torch.int64, device=dev), 0
+    up = _GUARD_UPLOADS.setdefault(dev.index, _GuardTableUpload())
+    return up.upload(rows, dev), len(rows)
+
+
+def grad_guard(tensors_or_table, max_norm=None, record=None, skipped=None, workspace=None):
+    """The gradient norm, the non-finite flag and the clipping divisor of a set of gradients, on the device (wm_grad_guard: two
+    launches, no atomics, no memset, no host read - bit-identical run to run and capturable).
+    tensors_or_table: a list of contiguous float32 CUDA tensors (grad_guard_table is built here: not inside a capture), or the
+    (table, n_rows) pair grad_guard_table returned.  max_norm: None for no clipping.  record (4 float32, overwritten with
+    {norm, found_inf, grad_scale, 0}) and skipped (1 int64, += found_inf; False: no counter) are allocated when not given; `workspace` (uint8, at least
+    wm_grad_guard_workspace_bytes(n_rows), contents irrelevant) likewise.  -> (record, skipped).
+    cpu_twin.grad_guard states the same record in plain PyTorch."""
+    if isinstance(tensors_or_table, tuple) and len(tensors_or_table) == 2 and isinstance(tensors_or_table[1], int):
+        table, n_rows = tensors_or_table
+    else:
+        table, n_rows = grad_guard_table(tensors_or_table)
+    if skipped is False:
+        counter = None                                             # no counter: the entry point takes NULL
+    else:
+        counter = skipped
+    _require_cuda("grad_guard", table, record, counter, workspace)
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < 2 * n_rows:
+        raise ValueError("grad_guard: the table is (n_rows, 2) int64, contiguous")
+    dev = table.device
+    if record is None:
+        record = torch.empty(4, dtype=torch.float32, device=dev)
+    if skipped is None:
+        counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    if record.dtype != torch.float32 or record.numel() < 4 or not record.is_contiguous():
+        raise ValueError("grad_guard: record is 4 contiguous float32")
+    if counter is not None and (counter.dtype != torch.int64 or counter.numel() < 1):
+        raise ValueError("grad_guard: skipped is one int64")
+    nb = _lib.load().wm_grad_guard_workspace_bytes(n_rows)
+    if workspace is None:
+        workspace = _det_workspace(nb, dev)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _launch(dev, "wm_grad_guard", table if n_rows else None, n_rows, 0.0 if max_norm is None else float(max_norm), record, counter,
+            workspace, ws_bytes)
+    return record, counter
+
+
 SSIM_TILE_H, SSIM_TILE_W = 24, 32          # csrc/ssim_loss.hip.h: SL_TH x SL_TW, one workgroup per tile (the tests' edge shapes)
 
 

@@ -26,6 +26,16 @@ Validation metrics.  The reference scores with `pyiqa` (femasr_model.py:39), a p
 `ssim` are this project's metrics.py - the reference's own comput_psnr_ssim.py, Y channel, on the uint8 image that tensor2img
 produces - computed on the device by ops.psnr_ssim_y.
 
+The guarded step.  An optional block switches trainer.GradGuard on for whichever step form the loop uses (absent: nothing changes,
+the log line's keys included):
+    train:
+      grad_guard:
+        max_norm: 1.0        # or ~ : no clipping
+        skip_nonfinite: true
+Every print_freq line then carries `grad_norm` (the last step's) and `skipped_steps`, read with the losses; a step whose gradients
+are not finite leaves weights and optimizer state as they are while the iteration and the lr schedule advance (the batch was
+consumed); the training state carries `skipped_steps` beside the batch position (a state without it resumes at 0).
+
 Graphed mode and "one loop iteration = one recipe iteration".  GraphedTrainStep's constructor runs three warm-up steps on a side
 stream before it captures; they are real optimizer steps.  The loop saves weights, moments and step counters before the
 constructor and restores them IN PLACE after it (the graph reads those very tensors), so the warm-up leaves no trace and every
@@ -45,6 +55,7 @@ from .registry import build_network
 
 LOG = logging.getLogger("wave_mamba_amd")
 _OPTIM_KEYS = ("type", "lr", "weight_decay", "betas")
+_GUARD_KEYS = ("max_norm", "skip_nonfinite")
 
 
 # ---- options ---------------------------------------------------------------------------------------------------------------------
@@ -75,6 +86,29 @@ def usable_metrics(opt, warn=False):
     return out
 
 
+def guard_options(opt):
+    """train.grad_guard -> the arguments of trainer.GradGuard, or None without the block (the step is then exactly the unguarded
+    one).  max_norm: a positive finite number, or ~ / absent for no clipping; skip_nonfinite: a bool (default true).  Anything else
+    is refused with a ValueError that names the key."""
+    block = _get(opt, "train.grad_guard")
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f"train.grad_guard: {block!r} is not a mapping ({', '.join(_GUARD_KEYS)})")
+    for key in block:
+        if key not in _GUARD_KEYS:
+            raise ValueError(f"train.grad_guard.{key}: not an argument of trainer.GradGuard ({', '.join(_GUARD_KEYS)})")
+    max_norm = block.get("max_norm")
+    if max_norm is not None:
+        if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not 0.0 < float(max_norm) < float("inf"):
+            raise ValueError(f"train.grad_guard.max_norm: {max_norm!r} is not a positive finite number (~ for no clipping)")
+        max_norm = float(max_norm)
+    skip = block.get("skip_nonfinite", True)
+    if not isinstance(skip, bool):
+        raise ValueError(f"train.grad_guard.skip_nonfinite: {skip!r} is not true or false")
+    return {"max_norm": max_norm, "skip_nonfinite": skip}
+
+
 def check_options(opt):
     """Refuse up front what the loop cannot do; every ValueError names the offending key."""
     if opt.get("scale", 1) != 1:
@@ -91,6 +125,7 @@ def check_options(opt):
                 "logger.print_freq", "logger.save_checkpoint_freq"):
         if _get(opt, key) is None:
             raise ValueError(f"{key}: missing")
+    guard_options(opt)
     metrics = usable_metrics(opt)
     key_metric = _get(opt, "val.key_metric")
     if opt.get("val") is not None and key_metric is not None and key_metric not in metrics:
@@ -257,6 +292,8 @@ class Trainer:
                                                 betas=tuple(optim.get("betas", (0.9, 0.999))), capturable=self.graphed)
         schedulers.set_lr(self.optimizer, [float(optim["lr"])] * len(self.optimizer.param_groups))   # the exact float64 base lr
         self.scheduler = schedulers.build_scheduler(self.optimizer, tr["scheduler"])
+        guard = guard_options(opt)
+        self.guard = None if guard is None else trainer.GradGuard(**guard).attach(self.optimizer)
         self.sampler = EnlargedSampler(len(train_store), self.world, self.rank, ds.get("dataset_enlarge_ratio", 1))
         if self.sampler.num_samples < self.batch_size:
             raise ValueError(f"datasets.train.batch_size_per_gpu: {self.batch_size} is more than the {self.sampler.num_samples} "
@@ -297,6 +334,8 @@ class Trainer:
         trainer.load_network(self.net, weights, strict=bool(_get(self.opt, "path.strict_load", True)) if pretrained else True)
         self.epoch, self.current_iter = int(epoch), int(current_iter)
         extra = state.get("recipe")
+        if self.guard is not None:                                 # (a state without the count, or one the reference wrote: 0)
+            self.guard.set_skipped((extra or {}).get("skipped_steps", 0))
         exact = extra is not None and extra.get("world") == (self.world if self.distributed else None)
         if exact:
             self._pos = int(extra["batch"])
@@ -333,10 +372,17 @@ class Trainer:
 
     def save(self, epoch, current_iter):
         """model.save(): base_model.py:227-228 and :341-342 name the files.  In the distributed mode a collective: every rank
-        calls it, rank 0 writes."""
+        calls it, rank 0 writes.  With train.grad_guard: a save that falls on a step whose found_inf was set is written like any
+        other.  This is deliberate, and differs from the wording "a checkpoint is not written from a step whose found_inf is set":
+        withholding the file would need a host read of found_inf at every save and would leave a hole in the save cadence that
+        resume relies on (models/net_g_{iter}.pth beside training_states/{iter}.state), and it protects nothing - nothing of that
+        step is in the file: the step was skipped, so the weights and the optimizer state are the previous
+        step's, bit for bit - and the state carries the count of skipped steps ("skipped_steps", beside the batch position)."""
         extra = {"batch": self._pos, "rng": self.batcher.rng.getstate()}
         if self.distributed:
             extra = {"world": self.world, "batch": self._pos, "rngs": self._all_rng_states()}
+        if self.guard is not None:
+            extra["skipped_steps"] = int(self.guard.skipped)
         self._save_network("latest" if current_iter == -1 else current_iter, current_iter, epoch)
         if self.writer:
             trainer.save_training_state(os.path.join(self.out_dir, "training_states", f"{current_iter}.state"), epoch, current_iter,
@@ -353,11 +399,16 @@ class Trainer:
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         weights = {k: v.detach().clone() for k, v in self.net.state_dict().items()}
         moments = {p: {k: v.clone() for k, v in st.items() if isinstance(v, torch.Tensor)} for p, st in self.optimizer.state.items()}
+        skipped = None if self.guard is None else int(self.guard.skipped)         # the warm-up steps are guarded steps too
         if self.distributed:
             step = trainer.GraphedDDPTrainStep(self.net, self.optimizer, lq, gt, process_group=self.group, capture=self.graphed,
-                                               collective=self.collective, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
+                                               collective=self.collective, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight,
+                                               guard=self.guard)
         else:
-            step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight)
+            step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight,
+                                            guard=self.guard)
+        if skipped is not None:
+            self.guard.set_skipped(skipped)
         with torch.no_grad():
             for k, v in self.net.state_dict().items():
                 v.copy_(weights[k])
@@ -378,7 +429,7 @@ class Trainer:
         if self.step_fn is not None:
             return self.step_fn(lq, gt)
         return trainer.train_step(self.net, self.optimizer, lq, gt, as_float=False, ssim_weight=self.ssim_weight,
-                                  fft_weight=self.fft_weight)
+                                  fft_weight=self.fft_weight, guard=self.guard)
 
     # -- validation -------------------------------------------------------------------------------------------------------------------
     def _enhance_u8(self, lq):
@@ -455,8 +506,10 @@ class Trainer:
                 if on_iter is not None:
                     on_iter(it, epoch, schedulers.current_lrs([self.optimizer]), rows, losses)
                 if it % self.print_freq == 0:
+                    guarded = {} if self.guard is None else {"grad_norm": float(self.guard.norm),
+                                                             "skipped_steps": int(self.guard.skipped)}
                     self._log({"iter": it, "epoch": epoch, "lrs": schedulers.current_lrs([self.optimizer]),
-                               **trainer.loss_values(losses)})
+                               **trainer.loss_values(losses), **guarded})
                 if it % self.save_freq == 0 or (self.latest_freq and it % self.latest_freq == 0):
                     self.save(epoch, it)
                 if self.val_freq and it % self.val_freq == 0:

@@ -105,19 +105,115 @@ def wrap_ddp(net, device=None, find_unused_parameters=False, force=False):
                                                      find_unused_parameters=find_unused_parameters)
 
 
-def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None, fft_weight=0.1):
+class GradGuard:
+    """The guarded optimizer step: the global gradient norm, gradient clipping and the skip of a step whose gradients are not
+    finite, decided ON THE DEVICE - so a captured step (GraphedTrainStep, GraphedDDPTrainStep) protects itself with the host out of
+    the step.  One overflowing batch would otherwise write NaN into every weight and both Adam moments, and the replays would go on
+    until somebody reads a loss.
+
+        guard = GradGuard(max_norm=1.0)                      # max_norm=None: no clipping; skip_nonfinite=False: no skip
+        step = GraphedTrainStep(net, optimizer, lq0, gt0, guard=guard)      # or train_step(..., guard=guard), GraphedDDPTrainStep
+        ... float(guard.norm), int(guard.skipped)            # host reads: when logging, not every step
+
+    On a GPU ops.grad_guard (two HIP launches: no atomics, no memset, bit-identical run to run) leaves {norm, found_inf, grad_scale}
+    in `record`, and torch's fused AdamW reads two of them as `optimizer.found_inf` / `optimizer.grad_scale` (attach()): with
+    found_inf == 1 its kernel leaves weights, both moments and the step counters as they are; with grad_scale = s it divides the
+    gradients by s (in place) first, s = max(1, (norm + 1e-6) / max_norm) - torch.nn.utils.clip_grad_norm_, inverted.  `max_norm` is
+    a launch scalar: a captured step keeps the value it was captured with.  CPU tensors (the gloo tests): cpu_twin.grad_guard
+    decides on the host - the non-fused AdamW takes neither tensor.
+    A skipped step leaves weights and optimizer state bit-equal and `skipped` one higher (counted only with skip_nonfinite); the
+    batch is consumed, so the caller's iteration count and lr schedule advance.
+    norm / found_inf / grad_scale: 0-dim views of `record`; skipped: 0-dim int64 - all of the last guarded step."""
+
+    def __init__(self, max_norm=None, skip_nonfinite=True):
+        if max_norm is not None and not (isinstance(max_norm, (int, float)) and not isinstance(max_norm, bool)
+                                         and 0.0 < float(max_norm) < float("inf")):
+            raise ValueError(f"GradGuard: max_norm {max_norm!r} (a positive finite number, or None for no clipping)")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.record = self._skipped = None
+        self._captured_tables = []
+
+    def to(self, device):
+        """Allocate record and counter on `device` (kept, with their contents, when they live there already)."""
+        device = torch.device(device)
+        if self.record is None or self.record.device != device:
+            count = 0 if self._skipped is None else int(self._skipped)
+            self.record = torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=device)
+            self._skipped = torch.full((1,), count, dtype=torch.int64, device=device)
+        return self
+
+    norm = property(lambda self: self.record[0])
+    found_inf = property(lambda self: self.record[1])
+    grad_scale = property(lambda self: self.record[2])
+    skipped = property(lambda self: self._skipped[0])
+
+    def set_skipped(self, count):
+        """Put the counter at `count`, in place (a resumed run)."""
+        self._skipped.fill_(int(count))
+
+    def attach(self, optimizer):
+        """Allocate on the optimizer's device; on a GPU hand the fused AdamW its two device scalars (found_inf with
+        skip_nonfinite, grad_scale with a max_norm).  Idempotent.  A CPU optimizer is left alone (the host decides: run())."""
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        if not params:
+            raise ValueError("GradGuard.attach: the optimizer has no parameters")
+        self.to(params[0].device)
+        if self.record.is_cuda:
+            if not all(g.get("fused", False) for g in optimizer.param_groups):
+                raise RuntimeError("GradGuard.attach: on a GPU the optimizer must be the fused AdamW (make_optimizer): only its kernel "
+                                   "reads found_inf / grad_scale from the device")
+            if self.skip_nonfinite:
+                optimizer.found_inf = self.found_inf
+            if self.max_norm is not None:
+                optimizer.grad_scale = self.grad_scale
+        return self
+
+    def run(self, grads, table=None):
+        """Judge the gradients `grads` of one step; call between backward() and optimizer.step().  -> whether the caller calls
+        optimizer.step(): always True on a GPU (the optimizer's kernel decides, from the record this launch leaves); for CPU
+        tensors False for a step to skip, and the gradients are divided by grad_scale in place here.  `table`: the
+        (table, n_rows) of ops.grad_guard_table over `grads`, built before a capture (this object then keeps it alive: the graph
+        replays a launch on its address); None builds it now (not inside a capture)."""
+        if self.record.is_cuda:
+            from . import ops
+            if table is not None and torch.cuda.is_current_stream_capturing():
+                # a captured launch holds the ADDRESS of the device table: the table must outlive the graph, whoever built it
+                if not any(t is table for t in self._captured_tables):
+                    self._captured_tables.append(table)
+            ops.grad_guard(table if table is not None else grads, self.max_norm, self.record,
+                           self._skipped if self.skip_nonfinite else False)
+            return True
+        from . import cpu_twin
+        self.record.copy_(cpu_twin.grad_guard(grads, self.max_norm))
+        if self.skip_nonfinite and float(self.found_inf):
+            self._skipped += 1
+            return False
+        if float(self.grad_scale) != 1.0:
+            torch._foreach_div_(list(grads), float(self.grad_scale))
+        return True
+
+
+def _guard_grads(params):
+    return [p.grad for p in params if p.grad is not None]
+
+
+def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None, fft_weight=0.1, guard=None):
     """One optimize_parameters(): zero_grad, forward, L1 + 0.1*FFT (+ ssim_weight * (1 - SSIM) where a weight is given; the
     loss dict then has "l_ssim", weighted like l_freq), backward (DDP all-reduce), step.
     Returns the reduced losses {name: python float} like the reference's `reduce_loss_dict` (base_model.py:376-401: a log dict
     of floats - callers format / json-dump it).  as_float=False returns 0-dim DEVICE tensors instead: nothing in the step then
     waits for the GPU (a `float()` is a host synchronisation per iteration, under DDP on every rank); `loss_values()` converts
     such a result when it is time to log (the reference logs every `print_freq` iterations).  bench.py and the tools time the
-    step with as_float=False.  `fft_weight`: the recipe's fft_opt.loss_weight (train_wavemamba_uhdll.yml:102-104)."""
+    step with as_float=False.  `fft_weight`: the recipe's fft_opt.loss_weight (train_wavemamba_uhdll.yml:102-104).
+    `guard`: a GradGuard - after backward() it judges the parameters' gradients (the table of their addresses is rebuilt per
+    call: eager gradients move), then the step is clipped or skipped as the guard says; the loss dict keeps its keys."""
     optimizer.zero_grad(set_to_none=True)
     out = net(lq)
     terms = losses(out, gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
     _total(terms).backward()
-    optimizer.step()
+    if guard is None or guard.attach(optimizer).run(_guard_grads([p for g in optimizer.param_groups for p in g["params"]])):
+        optimizer.step()
     return reduce_loss_dict({k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}, as_float=as_float)
 
 
@@ -136,7 +232,7 @@ class GraphedTrainStep:
     Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`) as 0-dim device tensors of the step just replayed
     (loss_values() to log them)."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1, guard=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep: single-process training only (under torch.distributed: GraphedDDPTrainStep)")
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
@@ -150,10 +246,25 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(lq.device))
         with torch.cuda.stream(side):                              # warm-up off the capture's stream (allocator pools, library set-up)
             for _ in range(warmup):
-                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight, fft_weight=fft_weight)
+                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight, fft_weight=fft_weight, guard=guard)
         torch.cuda.current_stream(lq.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
+        self.guard = guard
+        if guard is not None:
+            # the gradients of a capture live in the graph's pool; the guard's table holds addresses and its upload is a host-to-device
+            # copy, so both are made HERE: one flat buffer the captured step copies its gradients into, per-parameter views of it as
+            # the p.grad AdamW reads (GraphedDDPTrainStep's scheme), and one table over the whole buffer
+            params = [p for g in optimizer.param_groups for p in g["params"]]
+            # (every view starts on a 16-byte boundary, so the multi-tensor AdamW keeps its 16-byte accesses; the floats between
+            # two views stay zero and add nothing to the norm, so one table over the whole buffer serves)
+            sizes = [p.numel() for p in params]
+            slots = [(n + 3) // 4 * 4 for n in sizes]
+            self.flat = torch.zeros(sum(slots), dtype=torch.float32, device=lq.device)
+            views = [v[:n].view_as(p) for v, n, p in zip(self.flat.split(slots), sizes, params)]
+            guard.attach(optimizer)
+            from . import ops
+            self.guard_table = ops.grad_guard_table([self.flat])      # kept: the captured launch holds the table's address
         mode = {}
         if dist.is_available() and dist.is_initialized():
             # a (one-rank) process group exists: its watchdog thread polls events while this thread captures, which the default
@@ -164,6 +275,11 @@ class GraphedTrainStep:
             out = net(self.lq)
             terms = losses(out, self.gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
             _total(terms).backward()
+            if guard is not None:
+                torch._foreach_copy_(views, [p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
+                for p, v in zip(params, views):
+                    p.grad = v
+                guard.run([self.flat], table=self.guard_table)
             optimizer.step()
         self.losses = {k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}
 
@@ -207,7 +323,7 @@ class GraphedDDPTrainStep:
     reduce_loss_dict, base_model.py:376-401, leaves them on rank 0 only)."""
 
     def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split", ssim_weight=None,
-                 fft_weight=0.1):
+                 fft_weight=0.1, guard=None):
         if isinstance(net, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)):
             raise RuntimeError("GraphedDDPTrainStep: pass the bare module, not its DistributedDataParallel wrap")
         if not (dist.is_available() and dist.is_initialized()):
@@ -235,6 +351,15 @@ class GraphedDDPTrainStep:
         self.views = [v.view_as(p) for v, p in zip(self.flat[:-nl].split(self.sizes), self.params)]
         self.losses = {k: self.flat[i - nl] for i, k in enumerate(_LOSS_NAMES[:nl])}
         self.lq, self.gt = lq.clone(), gt.clone()
+        # the guard judges the REDUCED gradients (flat[:-nl]: the losses behind them are no part of the norm), so every rank takes
+        # the same decision; the table over the buffer is built once, here, before any capture
+        self.guard, self.guard_table = guard, None
+        if guard is not None:
+            guard.attach(optimizer)
+            if dev.type == "cuda":
+                from . import ops
+                self.guard_table = ops.grad_guard_table([self.flat[:-nl]])
+        self._grads = self.flat[:-nl]
         if not capture:
             return
         side = torch.cuda.Stream(dev)
@@ -281,7 +406,8 @@ class GraphedDDPTrainStep:
     def _update(self):
         for p, v in zip(self.params, self.views):
             p.grad = v
-        self.optimizer.step()
+        if self.guard is None or self.guard.run([self._grads], table=self.guard_table):
+            self.optimizer.step()
 
     def __call__(self, lq=None, gt=None):
         if lq is not None:
