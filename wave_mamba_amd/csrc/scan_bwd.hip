@@ -1,5 +1,6 @@
 // scan_bwd.hip - C ABI over the selective scan and the fused SS2D core, backward, and the linear weight gradient.
 #include "scan_common.h"
+#include "selscan_bwd.hip.h"
 #include "ss2d_core_bwd.hip.h"
 #include "linear_wgrad.hip.h"
 

@@ -26,18 +26,14 @@
 //                v_permlane32_swap -> v_permlane16_swap -> 4 DPP row-rotate adds (no LDS, no
 //                ds_bpermute).  dA / dD / dbias are per-chunk partials reduced by a last kernel.
 //
-// This file is the op-boundary scan's backward (wm_selscan_bwd) only.  The fused SS2D core's backward is
-// ss2d_core_bwd.hip.h, which borrows the constants, bwd_ld4 and the lane reductions from here.
+// This file is the op-boundary scan's backward (wm_selscan_bwd) only: its argument record, tile loading, the two kernels, the
+// finish and the slab sum.  What it shares with the fused SS2D core's backward (ss2d_core_bwd.hip.h) - the constants, bwd_ld4,
+// the lane reduction, the summary stores, softplus_grad - is scan_bwd_pieces.hip.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "selscan.hip.h"
+#include "scan_bwd_pieces.hip.h"
 
 namespace wm {
 
-constexpr int kBT = 16;            // steps per backward chunk (= one LDS tile)
-constexpr int kBS = 4;             // steps per register sub-tile
-constexpr int kBRow = 20;          // padded LDS row
 constexpr int kPartPad = 4;        // per-(chunk, channel) partial record: NP (dA) + [dD, dbias, 0, 0]
 
 struct ScanBwdArgs {
@@ -54,31 +50,6 @@ struct ScanBwdArgs {
                                    // slabs in the workspace and the workgroup of channel slice `sub` stores into slab `sub`
 };
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float row_sum16(float x) {       // every lane of a 16-lane row gets the row sum
-    x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), 0x128, 0xf, 0xf, false));  // row_ror:8
-    x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), 0x124, 0xf, 0xf, false));
-    x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), 0x122, 0xf, 0xf, false));
-    x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), 0x121, 0xf, 0xf, false));
-    return x;
-}
-// 32 per-lane values -> their sums over the 64 lanes; afterwards every lane of 16-lane row r holds
-// the totals of values 8r .. 8r+7 in out[0..7].
-__device__ __forceinline__ void wave_reduce32(const float (&v)[32], float (&out)[8]) {
-    float r1[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const u32x2 s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[j]), __float_as_uint(v[j + 16]), false, false);
-        r1[j] = __uint_as_float(s.x) + __uint_as_float(s.y);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const u32x2 s = __builtin_amdgcn_permlane16_swap(__float_as_uint(r1[j]), __float_as_uint(r1[j + 8]), false, false);
-        out[j] = row_sum16(__uint_as_float(s.x) + __uint_as_float(s.y));
-    }
-}
-
 struct BwdTileIdx { int b, g, nch, ch0; bool live; int d; };
 __device__ __forceinline__ BwdTileIdx bwd_decode(const ScanBwdArgs& p, int wr, int lane) {
     BwdTileIdx r;
@@ -89,15 +60,6 @@ __device__ __forceinline__ BwdTileIdx bwd_decode(const ScanBwdArgs& p, int wr, i
     r.live = lane < r.nch;
     r.d = r.ch0 + (r.live ? lane : 0);
     return r;
-}
-
-// 16-byte load that is UNCONDITIONAL (clamped to the array's first element when `ok` is false) and zeroed afterwards: an
-// `ok ? load : 0` compiles to a branch around the load with an s_waitcnt vmcnt(0) right behind it, so a tile's loads went
-// out one at a time, each waiting out its own latency (tools/train_breakdown.py --detail: the kernels of this file had a
-// floor of 30 / 63 us per launch however small the map).
-__device__ __forceinline__ float4 bwd_ld4(const float* __restrict__ base, long long off, bool ok) {
-    const float4 v = *reinterpret_cast<const float4*>(base + (ok ? off : 0LL));
-    return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
 }
 
 // cooperative load of one [64 rows][16 steps] tile (rows = this wave's channels) into LDS
@@ -229,17 +191,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_reduce_kernel(ScanBwdArgs p) {
         }
     }
     }                                                    // next chunk of the block
-    if (ix.live) {
-        const long long f = (long long)blockIdx.x * chains + row, m = (long long)(p.nblocks - 1 - (int)blockIdx.x) * chains + row;
-#pragma unroll
-        for (int q = 0; q < NP / 4; ++q) {
-            const float4 P4 = make_float4(pf[2 * q].x, pf[2 * q].y, pf[2 * q + 1].x, pf[2 * q + 1].y);
-            *reinterpret_cast<float4*>(p.wsP + f + 4 * q) = P4;
-            *reinterpret_cast<float4*>(p.wsPr + m + 4 * q) = P4;
-            *reinterpret_cast<float4*>(p.wsH + f + 4 * q) = make_float4(h[2 * q].x, h[2 * q].y, h[2 * q + 1].x, h[2 * q + 1].y);
-            *reinterpret_cast<float4*>(p.wsG + m + 4 * q) = make_float4(gl[2 * q].x, gl[2 * q].y, gl[2 * q + 1].x, gl[2 * q + 1].y);
-        }
-    }
+    if (ix.live) bwd_store_block_summaries(p, chains, row, pf, h, gl);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -417,7 +369,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_chunk_kernel(ScanBwdArgs p) {
                 const float ddt = (sdt.x + sdt.y) + ut * sb;
                 const float dut = fmaf(dt, sb, Dd * dyt);
                 float dd = ddt;
-                if (p.softplus) dd = xraw > 20.0f ? ddt : ddt / (1.0f + __expf(-xraw));
+                if (p.softplus) dd = softplus_grad(ddt, xraw);
                 dDp = fmaf(dyt, ut, dDp);
                 dbp += dd;
                 s_dy[lane * kBRow + tt] = dut;                        // du_t takes dy_t's slot
@@ -428,7 +380,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_chunk_kernel(ScanBwdArgs p) {
                     float v[32], o[8];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) { v[i] = prod[16 * half + i]; v[16 + i] = prod[NP + 16 * half + i]; }
-                    wave_reduce32(v, o);
+                    wave_reduce(v, o);
                     if ((lane & 15) == 0) {
                         const int rowg = lane >> 4;                   // row r holds values 8r .. 8r+7
 #pragma unroll
@@ -488,9 +440,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_chunk_kernel(ScanBwdArgs p) {
         // one partial record per block, layout [b*dim + d][block][NP + pad]: the finish kernel streams one channel's
         // partials contiguously
         float* pr = p.part + (((long long)ix.b * p.dim + ix.d) * p.nblocks + blockIdx.x) * (NP + kPartPad);
-#pragma unroll
-        for (int q = 0; q < NP / 4; ++q)
-            *reinterpret_cast<float4*>(pr + 4 * q) = make_float4(dA[2 * q].x, dA[2 * q].y, dA[2 * q + 1].x, dA[2 * q + 1].y);
+        bwd_store4(pr, dA);
         *reinterpret_cast<float4*>(pr + NP) = make_float4(dDp, dbp, 0.f, 0.f);
     }
 }

@@ -3,6 +3,7 @@
 // Reference: autograd of SS2D.forward_core (/root/reference/basicsr/archs/wavemamba_arch.py:446-478; reached from
 // basicsr/models/femasr_model.py:181): the x_proj / dt_proj einsums (:453-455) and the selective scan (:465-471) of one
 // direction over one layout (row-major map, or its transposed copy for the column directions).  Math: selscan_bwd.hip.h.
+// This file owns the fused kernels, their tile geometry and partial records; what it shares with that file: scan_bwd_pieces.hip.h.
 //
 // What changed against the first generation (selscan_bwd_{reduce,chunk}_kernel<., ., MODE 1 / 2> + ss2d_proj_kernel +
 // projbwd_dx_kernel + projgrad_kernel, 21.7 ms of a 78.7-ms BASELINE config-3 training step):
@@ -21,9 +22,7 @@
 //     over the block's chunks - the gradient planes (144 B per position and direction), projbwd_dx_kernel and
 //     projgrad_kernel are gone; per-block partials of every parameter gradient are added by ONE finish launch per call.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "selscan_bwd.hip.h"
+#include "scan_bwd_pieces.hip.h"
 #include "ss2d_core.hip.h"
 
 #ifndef WM_BWD_STAMP
@@ -124,20 +123,16 @@ __global__ __launch_bounds__(256) void core_bwd_prep_kernel(const float* __restr
     }
 }
 
-// 16 per-lane values -> their sums over the 64 lanes; afterwards every lane of 16-lane row r holds the totals of values
-// 4 r .. 4 r + 3 in out[0..3].
-__device__ __forceinline__ void wave_reduce16(const float (&v)[16], float (&out)[4]) {
-    float r1[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const u32x2 s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[j]), __float_as_uint(v[j + 8]), false, false);
-        r1[j] = __uint_as_float(s.x) + __uint_as_float(s.y);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32x2 s = __builtin_amdgcn_permlane16_swap(__float_as_uint(r1[j]), __float_as_uint(r1[j + 4]), false, false);
-        out[j] = row_sum16(__uint_as_float(s.x) + __uint_as_float(s.y));
-    }
+// dt before the softplus: the dt_projs row of this lane's channel applied to the step's dt_r record, plus the bias
+__device__ __forceinline__ float core_dt_raw(const float (&wdt)[4], float4 dr, float bias) {
+    return fmaf(wdt[3], dr.w, fmaf(wdt[2], dr.z, fmaf(wdt[1], dr.y, fmaf(wdt[0], dr.x, bias))));
+}
+// the three-product split MFMA: acc += a b without the lo x lo term
+__device__ __forceinline__ void core_mma3(const core_bf8& lo_a, const core_bf8& hi_a, const core_bf8& lo_b, const core_bf8& hi_b,
+                                          core_f4& acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo_a, hi_b, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi_a, lo_b, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi_a, hi_b, acc, 0, 0, 0);
 }
 
 // The B operands of the x_proj product from the staged x tile [64 channels][kBRow]: lane (c16 = step, g4) of K-step s2 holds
@@ -188,9 +183,7 @@ __device__ __forceinline__ void bwd_project_tile(int t, const uint4* __restrict_
     for (int s2 = 0; s2 < 2; ++s2) {
         const core_bf8 wh = *reinterpret_cast<const core_bf8*>(&wq[2 * s2]);
         const core_bf8 wl = *reinterpret_cast<const core_bf8*>(&wq[2 * s2 + 1]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, xh[s2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xl[s2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, xh[s2], acc, 0, 0, 0);
+        core_mma3(wl, wh, xl[s2], xh[s2], acc);
     }
     mfma_settle(acc);
     // D layout: lane holds rows 4 g4 .. 4 g4 + 3 of tile column c16 (= step)
@@ -284,10 +277,7 @@ __device__ __forceinline__ void core_bwd_reduce_body(const CoreBwdArgs& p, float
                 const float uu[4] = {u4.x, u4.y, u4.z, u4.w}, yy[4] = {y4.x, y4.y, y4.z, y4.w};
                 float xr[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float4 dr = *reinterpret_cast<const float4*>(&s_dtr[(4 * q + j) * 4]);
-                    xr[j] = fmaf(wdt[3], dr.w, fmaf(wdt[2], dr.z, fmaf(wdt[1], dr.y, fmaf(wdt[0], dr.x, bias))));
-                }
+                for (int j = 0; j < 4; ++j) xr[j] = core_dt_raw(wdt, *reinterpret_cast<const float4*>(&s_dtr[(4 * q + j) * 4]), bias);
                 const v2f da = softplus2((v2f){xr[0], xr[1]}), db = softplus2((v2f){xr[2], xr[3]});
                 const float dts[4] = {da.x, da.y, db.x, db.y};
 #pragma unroll
@@ -314,17 +304,7 @@ __device__ __forceinline__ void core_bwd_reduce_body(const CoreBwdArgs& p, float
             }
         }
     }
-    if (live) {
-        const long long f = (long long)blockIdx.x * chains + row, m = (long long)(p.nblocks - 1 - (int)blockIdx.x) * chains + row;
-#pragma unroll
-        for (int q = 0; q < NP / 4; ++q) {
-            const float4 P4 = make_float4(pf[2 * q].x, pf[2 * q].y, pf[2 * q + 1].x, pf[2 * q + 1].y);
-            *reinterpret_cast<float4*>(p.wsP + f + 4 * q) = P4;
-            *reinterpret_cast<float4*>(p.wsPr + m + 4 * q) = P4;
-            *reinterpret_cast<float4*>(p.wsH + f + 4 * q) = make_float4(h[2 * q].x, h[2 * q].y, h[2 * q + 1].x, h[2 * q + 1].y);
-            *reinterpret_cast<float4*>(p.wsG + m + 4 * q) = make_float4(gl[2 * q].x, gl[2 * q].y, gl[2 * q + 1].x, gl[2 * q + 1].y);
-        }
-    }
+    if (live) bwd_store_block_summaries(p, chains, row, pf, h, gl);
 }
 
 // grid (nblocks, B, 4): blockIdx.z = direction - row layout forward (a0) / reversed (a2), column layout (the transposed copies)
@@ -452,10 +432,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
         for (int q = 0; q < kBT / 4; ++q) {
             float xr[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 dr = *reinterpret_cast<const float4*>(&s_dtr[(4 * q + j) * 4]);
-                xr[j] = fmaf(wdt[3], dr.w, fmaf(wdt[2], dr.z, fmaf(wdt[1], dr.y, fmaf(wdt[0], dr.x, bias))));
-            }
+            for (int j = 0; j < 4; ++j) xr[j] = core_dt_raw(wdt, *reinterpret_cast<const float4*>(&s_dtr[(4 * q + j) * 4]), bias);
             const v2f da = softplus2((v2f){xr[0], xr[1]}), db = softplus2((v2f){xr[2], xr[3]});
             *reinterpret_cast<float4*>(&s_d[lane * kBRow + 4 * q]) = make_float4(da.x, da.y, db.x, db.y);
         }
@@ -583,7 +560,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                         psb[j] = sdu.x + sdu.y;
                         psd[j] = sdt.x + sdt.y;
                         float o[4];
-                        wave_reduce16(prod, o);           // (dead lanes hold zeros: their u, dy rows are zero-filled)
+                        wave_reduce(prod, o);           // (dead lanes hold zeros: their u, dy rows are zero-filled)
                         if ((lane & 15) == 0) {
                             const int rg = lane >> 4;     // row rg holds values 4 rg .. 4 rg + 3: 0..7 dB n, 8..15 dC n (n local)
                             float* dst = s_red + ((rg >> 1) * NP + 8 * w + 4 * (rg & 1)) * kBRow + tt;
@@ -618,9 +595,9 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                     }
                     const float ut = s_u[lane * kBRow + tt], dyt = s_dy[lane * kBRow + tt], dt = s_d[lane * kBRow + tt];
                     const float4 dr = *reinterpret_cast<const float4*>(&s_dtr[tt * 4]);
-                    const float xraw = fmaf(wdt[3], dr.w, fmaf(wdt[2], dr.z, fmaf(wdt[1], dr.y, fmaf(wdt[0], dr.x, bias))));
+                    const float xraw = core_dt_raw(wdt, dr, bias);
                     const float ddt = sd + ut * sb;
-                    dd = xraw > 20.0f ? ddt : ddt / (1.0f + __expf(-xraw));
+                    dd = softplus_grad(ddt, xraw);
                     dDp = fmaf(dyt, ut, dDp);
                     dbp += dd;
                     dwp[0] = fmaf(dd, dr.x, dwp[0]); dwp[1] = fmaf(dd, dr.y, dwp[1]);
@@ -637,7 +614,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                     for (int i = 0; i < 16; ++i) v[i] = 0.0f;
 #pragma unroll
                     for (int s = 0; s < SPW; ++s) { v[2 * s] = ddv[s] * wdt[2 * pr]; v[2 * s + 1] = ddv[s] * wdt[2 * pr + 1]; }
-                    wave_reduce16(v, o);
+                    wave_reduce(v, o);
                     if ((lane & 15) == 0) {
                         const int rg = lane >> 4;
 #pragma unroll
@@ -679,9 +656,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                         const uint4 wh4 = p.wT[((t * KS + s) * 2 + 0) * 64 + lane], wl4 = p.wT[((t * KS + s) * 2 + 1) * 64 + lane];
                         const core_bf8 wh = *reinterpret_cast<const core_bf8*>(&wh4);
                         const core_bf8 wl = *reinterpret_cast<const core_bf8*>(&wl4);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, gh[s], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, gl[s], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, gh[s], acc, 0, 0, 0);
+                        core_mma3(wl, wh, gl[s], gh[s], acc);
                     }
                     mfma_settle(acc);
 #pragma unroll
@@ -714,10 +689,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
                 split8(&s_red[grow * kBRow + 8 * (kq & 1)], (rt > 0 || i16 < 4) ? km : 0.0f, ah, al);
 #pragma unroll
                 for (int c = 0; c < 4 / NW; ++c) {
-                    core_f4& acc = wacc[rt * (4 / NW) + c];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[c], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[c], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[c], acc, 0, 0, 0);
+                    core_mma3(al, ah, bl[c], bh[c], wacc[rt * (4 / NW) + c]);
                 }
             }
         }
@@ -783,9 +755,7 @@ __global__ __launch_bounds__(64 * BwdCfg<NP>::NW, 2) void core_bwd_chunk_kernel(
     __syncthreads();
     if (live) {
         float* pr = p.part + (((long long)b * p.dim + d) * p.nblocks + blockIdx.x) * (NP + kPartPadFused);
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            *reinterpret_cast<float4*>(pr + 8 * w + 4 * q) = make_float4(dA[2 * q].x, dA[2 * q].y, dA[2 * q + 1].x, dA[2 * q + 1].y);
+        bwd_store4(pr + 8 * w, dA);
         if (w == 0) {
             float t6[6];
 #pragma unroll
