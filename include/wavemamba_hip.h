@@ -474,6 +474,32 @@ int wm_ssim_mean_fwd(const float* a, const float* b, float* out, float* p1, floa
 int wm_ssim_mean_bwd(const float* x, const float* other, const float* p, const float* q, const float* r, const float* gout,
                      float* gx, int64_t planes, int H, int W, void* stream);
 
+/* The FFT training loss: FFTLoss of basicsr/losses/losses.py:300-313 (L1 mean between the stacked real / imaginary parts of
+ * rfft2(pred) and rfft2(target); options/train_wavemamba_uhdll.yml:102-104 weights it by 0.1, `fft_opt`) - csrc/fft_loss.hip.h.
+ * rfft2 is linear: d = a - b is taken in fp32 first and transformed ONCE, and no spectrum exists as a tensor.
+ * a, b: `planes` (= B C) dense fp32 planes of H x W, 16-byte aligned; H and W powers of two in [16, 1024]; K = W / 2 + 1.
+ *   Y[k1, k2] = sum d[n1, n2] exp(-2 pi i (k1 n1 / H + k2 n2 / W)), k2 < K;  out[0] = sum(|Re Y| + |Im Y|) / M, M = planes H K 2
+ *   ga[n1, n2] = gout[0] / M * Re sum_{k1, k2 < K} s[k1, k2] exp(+2 pi i (k1 n1 / H + k2 n2 / W)), s = sign(Re Y) + i sign(Im Y),
+ *   sign(0) = 0 (the half spectrum only, no Hermitian doubling, no 1 / HW: autograd's gradient of the reference composition); the
+ *   imaginary sign of the four self-conjugate bins (k1 in {0, H / 2}, k2 in {0, W / 2}) counts as 0.  gb = -ga.
+ *   wm_fft_l1_supported: 1 when H and W are powers of two in [16, 1024], else 0.
+ *   wm_fft_l1_record_bytes: what forward leaves for backward (one byte per bin); wm_fft_l1_workspace_bytes: the workgroups' float64
+ *     partial sums and one complex fp32 half spectrum of the difference, the same size for both directions.  Both 0 for an
+ *     unsupported shape (WM_EUNSUPPORTED from the launching entries: a size that is no power of two in [16, 1024], or more planes
+ *     than one launch holds - 2^24 - 1 workgroups).  The workspace is 16-byte aligned and written before it is read.
+ *   wm_fft_l1_mean_fwd: three launches; per-workgroup sums in float64, added in a fixed order by a kernel that OVERWRITES out: no
+ *     atomics, no memset, bit-identical run to run.  record: wm_fft_l1_record_bytes bytes, or NULL for the value alone.
+ *   wm_fft_l1_mean_bwd: two launches; gout one device float (read on the device); ga and / or gb (NULL: not wanted; 16-byte
+ *     aligned).  The record is only read: a second backward from it gives the same bits.
+ * No host synchronisation, no allocation: everything runs on `stream` and can be captured into a graph. */
+int wm_fft_l1_supported(int H, int W);
+size_t wm_fft_l1_record_bytes(int64_t planes, int H, int W);
+size_t wm_fft_l1_workspace_bytes(int64_t planes, int H, int W);
+int wm_fft_l1_mean_fwd(const float* a, const float* b, float* out, void* record, void* workspace, size_t workspace_bytes,
+                       int64_t planes, int H, int W, void* stream);
+int wm_fft_l1_mean_bwd(const void* record, const float* gout, float* ga, float* gb, void* workspace, size_t workspace_bytes,
+                       int64_t planes, int H, int W, void* stream);
+
 /* Image-quality metrics of the reference's evaluation loop (inference_wavemamba.py:116-117, :133-134 -> comput_psnr_ssim.py with
  * crop_border, input_order 'HWC' / 'CHW', test_y_channel = True), csrc/metrics.hip.h.
  *   Images: N uint8 images of H x W x 3, element (n, h, w, ch) at n sn + h sh + w sw + ch sc (strides in elements, >= 0: HWC and

@@ -9,6 +9,7 @@
 """
 from . import _lib, ops, registry, trainer, inference, metrics, data, schedulers   # noqa: F401
 from .ops import set_deterministic, is_deterministic   # noqa: F401
+from .ops import set_fft_loss, fft_loss_backend         # noqa: F401
 from .registry import ARCH_REGISTRY, build_network   # noqa: F401
 from .archs import wavemamba_arch           # noqa: F401  (registers 'WaveMamba')
 from .archs.wavemamba_arch import WaveMamba  # noqa: F401

@@ -72,6 +72,11 @@ SIGNATURES = {
     "wm_ssim_workspace_bytes": (_sz, [_i64, _i, _i]),
     "wm_ssim_mean_fwd": (_i, [_p] * 8 + [_sz, _i64, _i, _i, _p]),
     "wm_ssim_mean_bwd": (_i, [_p] * 7 + [_i64, _i, _i, _p]),
+    "wm_fft_l1_supported": (_i, [_i, _i]),
+    "wm_fft_l1_record_bytes": (_sz, [_i64, _i, _i]),
+    "wm_fft_l1_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wm_fft_l1_mean_fwd": (_i, [_p] * 5 + [_sz, _i64, _i, _i, _p]),
+    "wm_fft_l1_mean_bwd": (_i, [_p] * 5 + [_sz, _i64, _i, _i, _p]),
     "wm_gate_fwd": (_i, [_p] * 3 + [_i, _i] + [_i64] * 4 + [_p]),
     "wm_gate_bwd": (_i, [_p] * 5 + [_i, _i] + [_i64] * 6 + [_p]),
     "wm_scale_add_fwd": (_i, [_p] * 4 + [_i, _i, _i64, _p]),

@@ -146,6 +146,21 @@ def ssim_mean(img1, img2):
     return s_map.mean().to(img1.dtype)
 
 
+def fft_l1_mean(pred, target):
+    """FFTLoss at loss_weight 1 (losses.py:300-313: l1_loss between stack([rfft2(x).real, rfft2(x).imag]) of pred and of target)
+    for (B, C, H, W) tensors of any float dtype, any H and W, stated as the HIP kernels compute it: rfft2 is linear, so the
+    DIFFERENCE is transformed, once, and the mean of |Re| + |Im| over its half spectrum is the loss.  Evaluated in the inputs'
+    dtype (float32 for the 16-bit ones) and returned in it; differentiable by autograd.  In float32 this form keeps the sign of
+    each bin where the reference's takes it from a small difference of two large spectra."""
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise RuntimeError(f"fft_l1_mean: expected two (B, C, H, W) tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if pred.numel() == 0:
+        raise RuntimeError("fft_l1_mean: empty input")
+    work = pred.dtype if pred.dtype in (torch.float32, torch.float64) else torch.float32
+    y = torch.fft.rfft2(pred.to(work) - target.to(work))
+    return ((y.real.abs().sum() + y.imag.abs().sum()) / (2 * y.numel())).to(pred.dtype)
+
+
 # out[i, j] = A[r, c] for the eight modes of data_augmentation (transforms.py:223-268): (r from j?, r mirrored?, c mirrored?)
 _AUG_MODES = ((False, False, False), (False, True, False), (True, False, True), (True, False, False),
               (False, True, True), (False, False, True), (True, True, False), (True, True, True))

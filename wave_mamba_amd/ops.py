@@ -1931,6 +1931,112 @@ def ssim_mean(img1, img2):
                            grad and img2.requires_grad)
 
 
+FFT_L1_SIZE_RULE = "H and W powers of two in [16, 1024]"      # csrc/fft_loss.hip.h (wm_fft_l1_supported states it in the library)
+
+
+def fft_l1_supported(H, W):
+    """Whether the fused FFT loss has kernels for planes of H x W (the library's own answer: wm_fft_l1_supported)."""
+    return bool(getattr(_lib.load(), "wm_fft_l1_supported")(int(H), int(W)))
+
+
+def _fft_l1_sizes(planes, H, W):
+    """(record bytes, workspace bytes) of the fused FFT loss; raises with the size rule where the library has no kernel."""
+    lib = _lib.load()                      # (by name: tests/test_cabi.py lists the entry points this file may call as attributes)
+    rec, ws = getattr(lib, "wm_fft_l1_record_bytes")(planes, H, W), lib.wm_fft_l1_workspace_bytes(planes, H, W)
+    if rec == 0 or ws == 0:
+        raise RuntimeError(f"fft_l1_mean: no kernel for {planes} planes of {H} x {W}: {FFT_L1_SIZE_RULE}, and at most 2^24 - 1 "
+                           "workgroups in a launch")
+    return rec, ws
+
+
+def _fft_l1_forward(a, b, want):
+    """wm_fft_l1_mean_fwd on dense fp32 (B, C, H, W): (loss 0-dim, record) - the record (a byte per spectrum bin: the signs) only
+    where a gradient is wanted."""
+    B, C, H, W = a.shape
+    rec_bytes, ws_bytes = _fft_l1_sizes(B * C, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+    out = torch.empty(1, dtype=torch.float32, device=a.device)
+    rec = torch.empty(rec_bytes, dtype=torch.uint8, device=a.device) if want else None
+    _launch(a.device, "wm_fft_l1_mean_fwd", a, b, out, rec, ws, ws_bytes, B * C, H, W)
+    return out.reshape(()), rec
+
+
+def _fft_l1_backward(rec, g, shape, want_a, want_b):
+    """wm_fft_l1_mean_bwd: (ga, gb), each only where wanted; gb = -ga comes out of the same launch."""
+    B, C, H, W = shape
+    _, ws_bytes = _fft_l1_sizes(B * C, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=rec.device)
+    ga = torch.empty(shape, dtype=torch.float32, device=rec.device) if want_a else None
+    gb = torch.empty(shape, dtype=torch.float32, device=rec.device) if want_b else None
+    _launch(rec.device, "wm_fft_l1_mean_bwd", rec, g, ga, gb, ws, ws_bytes, B * C, H, W)
+    return ga, gb
+
+
+class _FFTL1Mean(torch.autograd.Function):
+    """FFTLoss (losses.py:300-313) of two dense fp32 (B, C, H, W) tensors on the HIP kernels of fft_loss.hip.h: one transform of
+    a - b, the L1 mean of its half spectrum summed in a fixed order (bit-equal run to run in every mode, capturable).  Where a
+    gradient is wanted (decided by fft_l1_mean() - grad mode is off in here) the forward keeps the signs of the spectrum, a byte
+    per bin, and backward transforms them back: two launches for both gradients."""
+
+    @staticmethod
+    def forward(ctx, a, b, want_a, want_b):
+        out, rec = _fft_l1_forward(a, b, want_a or want_b)
+        ctx.want = (want_a, want_b)
+        ctx.shape = tuple(a.shape)
+        ctx.save_for_backward(rec)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        rec, = ctx.saved_tensors
+        want_a, want_b = (ctx.want[i] and ctx.needs_input_grad[i] for i in (0, 1))
+        if not (want_a or want_b):
+            return None, None, None, None
+        ga, gb = _fft_l1_backward(rec, g.contiguous().float(), ctx.shape, want_a, want_b)
+        return ga, gb, None, None
+
+
+def fft_l1_mean(pred, target):
+    """FFTLoss()(pred, target) at loss_weight 1 (losses.py:300-313: the L1 mean between the stacked real / imaginary parts of the
+    two rfft2) for CUDA tensors (B, C, H, W) of one shape, H and W powers of two in [16, 1024]: a 0-dim fp32 tensor, differentiable
+    in both arguments.  The difference is taken first and transformed once (fft_loss.hip.h); cpu_twin.fft_l1_mean states the same."""
+    _require_cuda("fft_l1_mean", pred, target)
+    if pred.dim() != 4 or target.dim() != 4:
+        raise RuntimeError(f"fft_l1_mean: expected (B, C, H, W) tensors, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if pred.shape != target.shape:
+        raise RuntimeError(f"fft_l1_mean: shapes differ: {tuple(pred.shape)} vs {tuple(target.shape)}")
+    if pred.numel() == 0:
+        raise RuntimeError("fft_l1_mean: empty input")
+    if not fft_l1_supported(pred.shape[2], pred.shape[3]):
+        raise RuntimeError(f"fft_l1_mean: no kernel for planes of {pred.shape[2]} x {pred.shape[3]}: {FFT_L1_SIZE_RULE}")
+    grad = torch.is_grad_enabled()
+    return _FFTL1Mean.apply(pred.contiguous().float(), target.contiguous().float(), grad and pred.requires_grad,
+                            grad and target.requires_grad)
+
+
+# Which code computes the FFT term of the training loss (trainer.fft_l1): "torch" - torch.fft.rfft2 of both images and ops.l1_mean
+# over the spectra, as always - or "hip" - fft_l1_mean above, for the shapes it has kernels for.  Off ("torch") by default; WM_FFT_LOSS
+# in the environment sets the initial value (read at import, like WM_TRAIN_CONV).  Read when the loss is CALLED: a graph captured
+# under one backend replays that backend.
+_FFT_LOSS_BACKENDS = ("torch", "hip")
+_FFT_LOSS = os.environ.get("WM_FFT_LOSS", "torch")
+if _FFT_LOSS not in _FFT_LOSS_BACKENDS:
+    raise RuntimeError(f"WM_FFT_LOSS={_FFT_LOSS!r}: one of {_FFT_LOSS_BACKENDS}")
+
+
+def set_fft_loss(backend):
+    """Choose the FFT loss's backend, "torch" or "hip" (see above).  Returns the previous one."""
+    global _FFT_LOSS
+    if backend not in _FFT_LOSS_BACKENDS:
+        raise ValueError(f"set_fft_loss: {backend!r} is not one of {_FFT_LOSS_BACKENDS}")
+    prev, _FFT_LOSS = _FFT_LOSS, backend
+    return prev
+
+
+def fft_loss_backend():
+    return _FFT_LOSS
+
+
 class _Conv2dTrain(torch.autograd.Function):
     """Dense 3x3 / 1x1 convolution (stride 1, 'same' padding) for training: forward and input gradient on the
     matrix-core kernels (the input gradient is the same convolution with the weight transposed and flipped) - the fp16 form

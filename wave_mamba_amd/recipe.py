@@ -109,6 +109,15 @@ def guard_options(opt):
     return {"max_norm": max_norm, "skip_nonfinite": skip}
 
 
+def fft_backend_option(opt):
+    """train.fft_opt.backend (this project's key, optional): `hip` - the fused FFT loss (ops.fft_l1_mean) - or `torch`.  Absent ->
+    None: the process default (ops.set_fft_loss / WM_FFT_LOSS), so a recipe without the key trains as it always did."""
+    backend = _get(opt, "train.fft_opt.backend")
+    if backend is not None and backend not in ("hip", "torch"):
+        raise ValueError(f"train.fft_opt.backend: {backend!r} is not one of hip, torch")
+    return backend
+
+
 def check_options(opt):
     """Refuse up front what the loop cannot do; every ValueError names the offending key."""
     if opt.get("scale", 1) != 1:
@@ -126,6 +135,7 @@ def check_options(opt):
         if _get(opt, key) is None:
             raise ValueError(f"{key}: missing")
     guard_options(opt)
+    fft_backend_option(opt)
     metrics = usable_metrics(opt)
     key_metric = _get(opt, "val.key_metric")
     if opt.get("val") is not None and key_metric is not None and key_metric not in metrics:
@@ -272,6 +282,7 @@ class Trainer:
         seed = opt.get("manual_seed")
         self.batch_size = int(ds["batch_size_per_gpu"])
         self.fft_weight = float(_get(opt, "train.fft_opt.loss_weight", 0.1))
+        self.fft_backend = fft_backend_option(opt)
         ssim = _get(opt, "train.pixel_ssim_opt.loss_weight")
         self.ssim_weight = None if ssim is None else float(ssim)
         self.warmup_iter = int(tr.get("warmup_iter", -1))
@@ -403,10 +414,10 @@ class Trainer:
         if self.distributed:
             step = trainer.GraphedDDPTrainStep(self.net, self.optimizer, lq, gt, process_group=self.group, capture=self.graphed,
                                                collective=self.collective, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight,
-                                               guard=self.guard)
+                                               guard=self.guard, fft_backend=self.fft_backend)
         else:
             step = trainer.GraphedTrainStep(self.net, self.optimizer, lq, gt, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight,
-                                            guard=self.guard)
+                                            guard=self.guard, fft_backend=self.fft_backend)
         if skipped is not None:
             self.guard.set_skipped(skipped)
         with torch.no_grad():
@@ -429,7 +440,7 @@ class Trainer:
         if self.step_fn is not None:
             return self.step_fn(lq, gt)
         return trainer.train_step(self.net, self.optimizer, lq, gt, as_float=False, ssim_weight=self.ssim_weight,
-                                  fft_weight=self.fft_weight, guard=self.guard)
+                                  fft_weight=self.fft_weight, guard=self.guard, fft_backend=self.fft_backend)
 
     # -- validation -------------------------------------------------------------------------------------------------------------------
     def _enhance_u8(self, lq):

@@ -1,7 +1,7 @@
 """The hot-path operators as torch.library custom ops (namespace `wavemamba_hip`), for hosts that bind operators by name -
 torch.compile / torch.export graphs, C++ frontends, other packages - instead of importing `wave_mamba_amd.ops`
 ("torch.library custom ops with registered backward named wavemamba_hip::{dwt2d, idwt2d, selective_scan,
-ss2d_core}"), and the SSIM training loss beside them.
+ss2d_core}"), and the SSIM and FFT training losses beside them.
 
     import wave_mamba_amd.torch_ops            # registers the ops (idempotent)
     ll, hl, lh, hh = torch.ops.wavemamba_hip.dwt2d(x)                       # dwt_init          (wavemamba_arch.py:97-110)
@@ -9,6 +9,7 @@ ss2d_core}"), and the SSIM training loss beside them.
     out = torch.ops.wavemamba_hip.selective_scan(u, delta, A, B, C, D, delta_bias, True)   # selective_scan_fn (:465-471)
     y0, y1, y2, y3 = torch.ops.wavemamba_hip.ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)  # (:446-478)
     s = torch.ops.wavemamba_hip.ssim_mean(pred, gt)                        # SSIM()           (basicsr/models/cal_ssim.py:39-64)
+    f = torch.ops.wavemamba_hip.fft_l1_mean(pred, gt)                      # FFTLoss()        (basicsr/losses/losses.py:300-313)
 
 Every op is a thin shell over the C ABI calls `ops.py` makes (same kernels, same checks) under the CUDA dispatch key, has a
 fake (meta) implementation so that tracing never launches anything, and an autograd formula whose backward is itself a
@@ -175,6 +176,41 @@ def _ssim_mean_backward_fake(img1, img2, gout, need1, need2):
     return (f(img1) if need1 else z), (f(img2) if need2 else z)
 
 
+# ---- FFT training loss --------------------------------------------------------------------------------------------------
+def _fft_l1_check(pred, target):
+    torch._check(pred.dim() == 4 and pred.shape == target.shape,
+                 lambda: f"fft_l1_mean: expected two (B, C, H, W) tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    torch._check(pred.numel() > 0, lambda: "fft_l1_mean: empty input")
+
+
+def _fft_l1_mean(pred, target):
+    _fft_l1_check(pred, target)
+    return ops._fft_l1_forward(pred.detach().contiguous().float(), target.detach().contiguous().float(), False)[0]
+
+
+def _fft_l1_mean_fake(pred, target):
+    _fft_l1_check(pred, target)
+    return pred.new_empty((), dtype=torch.float32)
+
+
+def _fft_l1_mean_backward(pred, target, gout, need1, need2):
+    """The op's forward keeps no record (its output is the value alone), so the signs are made here: one more forward than
+    ops.fft_l1_mean's backward, then the same gradient kernels - the same bits."""
+    a, b = pred.detach().contiguous().float(), target.detach().contiguous().float()
+    z = a.new_zeros((0,))
+    if not (need1 or need2):
+        return z, z
+    _, rec = ops._fft_l1_forward(a, b, True)
+    ga, gb = ops._fft_l1_backward(rec, gout.contiguous().float(), tuple(a.shape), need1, need2)
+    return (ga if need1 else z), (gb if need2 else z)
+
+
+def _fft_l1_mean_backward_fake(pred, target, gout, need1, need2):
+    z = pred.new_empty((0,), dtype=torch.float32)
+    f = lambda t: t.new_empty(t.shape, dtype=torch.float32)
+    return (f(pred) if need1 else z), (f(target) if need2 else z)
+
+
 _define("dwt2d", "(Tensor x) -> (Tensor, Tensor, Tensor, Tensor)", _dwt2d, _dwt2d_fake)
 _define("dwt2d_backward", "(Tensor g_ll, Tensor g_hl, Tensor g_lh, Tensor g_hh) -> Tensor", _dwt2d_backward, _dwt2d_backward_fake)
 _define("idwt2d", "(Tensor x) -> Tensor", _idwt2d, _idwt2d_fake)
@@ -192,7 +228,9 @@ _define("ss2d_core_backward", "(Tensor x, Tensor x_proj_weight, Tensor dt_projs_
 _define("ssim_mean", "(Tensor img1, Tensor img2) -> Tensor", _ssim_mean, _ssim_mean_fake)
 _define("ssim_mean_backward", "(Tensor img1, Tensor img2, Tensor gout, bool need1, bool need2) -> (Tensor, Tensor)",
         _ssim_mean_backward, _ssim_mean_backward_fake)
-
+_define("fft_l1_mean", "(Tensor pred, Tensor target) -> Tensor", _fft_l1_mean, _fft_l1_mean_fake)
+_define("fft_l1_mean_backward", "(Tensor pred, Tensor target, Tensor gout, bool need1, bool need2) -> (Tensor, Tensor)",
+        _fft_l1_mean_backward, _fft_l1_mean_backward_fake)
 
 
 # ---- CPU dispatch key: the plain-PyTorch twins --------------------------------------------------------------------------
@@ -246,6 +284,16 @@ def _ssim_mean_backward_cpu(img1, img2, gout, need1, need2):
 
 
 _cpu("ssim_mean_backward", _ssim_mean_backward_cpu)
+_cpu("fft_l1_mean", lambda pred, target: cpu_twin.fft_l1_mean(pred, target).float())
+
+
+def _fft_l1_mean_backward_cpu(pred, target, gout, need1, need2):
+    ga, gb = _twin_vjp(cpu_twin.fft_l1_mean, [pred, target], [gout.to(pred.dtype)])
+    z = pred.new_zeros((0,), dtype=torch.float32)
+    return (ga.float() if need1 else z), (gb.float() if need2 else z)
+
+
+_cpu("fft_l1_mean_backward", _fft_l1_mean_backward_cpu)
 
 _o = torch.ops.wavemamba_hip
 
@@ -319,5 +367,15 @@ def _ssim_autograd(ctx, g):
 
 torch.library.register_autograd(f"{_NS}::ssim_mean", _ssim_autograd, setup_context=_ssim_setup, lib=_lib_def)
 
+
+def _fft_l1_autograd(ctx, g):
+    pred, target = ctx.saved_tensors
+    need1, need2 = ctx.needs_input_grad
+    g1, g2 = _o.fft_l1_mean_backward(pred, target, g.contiguous(), need1, need2)
+    return (g1.to(pred.dtype) if need1 else None), (g2.to(target.dtype) if need2 else None)
+
+
+torch.library.register_autograd(f"{_NS}::fft_l1_mean", _fft_l1_autograd, setup_context=_ssim_setup, lib=_lib_def)
+
 OPS = ("dwt2d", "dwt2d_backward", "idwt2d", "idwt2d_backward", "selective_scan", "selective_scan_backward", "ss2d_core",
-       "ss2d_core_backward", "ssim_mean", "ssim_mean_backward")
+       "ss2d_core_backward", "ssim_mean", "ssim_mean_backward", "fft_l1_mean", "fft_l1_mean_backward")

@@ -36,9 +36,20 @@ def l1(pred, target):
     return F.l1_loss(pred, target)
 
 
-def fft_l1(pred, target):
+def fft_l1(pred, target, backend=None):
     """FFTLoss (losses.py:306-313): L1 between the stacked real/imag parts of rfft2.  On the GPU the same mean is taken over the
-    interleaved (re, im) floats of the complex tensors (`view_as_real`: the stacked copies are never made)."""
+    interleaved (re, im) floats of the complex tensors (`view_as_real`: the stacked copies are never made).
+    `backend`: None - the process default (ops.set_fft_loss / WM_FFT_LOSS; "torch" unless chosen otherwise) - "torch" or "hip".
+    "hip" takes the fused kernels (ops.fft_l1_mean: one transform of pred - target, a fixed-order sum, no rocFFT plan and no
+    spectrum tensor) for fp32 device tensors (B, C, H, W) whose H and W it has kernels for (ops.fft_l1_supported), and the path
+    above for everything else, so a step never dies on a crop size."""
+    from . import ops
+    if backend is None:
+        backend = ops.fft_loss_backend()
+    elif backend not in ("torch", "hip"):
+        raise ValueError(f"fft_l1: backend {backend!r} is not one of ('torch', 'hip')")
+    if backend == "hip" and _on_hip(pred, target) and pred.dim() == 4 and ops.fft_l1_supported(pred.shape[2], pred.shape[3]):
+        return ops.fft_l1_mean(pred, target)
     pf, tf = torch.fft.rfft2(pred), torch.fft.rfft2(target)
     if pf.is_cuda and pf.dtype == torch.complex64 and tf.dtype == torch.complex64:
         return l1(torch.view_as_real(pf), torch.view_as_real(tf))
@@ -57,11 +68,12 @@ def ssim_loss(pred, target):
     return 1 - cpu_twin.ssim_mean(pred, target)
 
 
-def losses(output, gt, fft_weight=0.1, ssim_weight=None):
-    """(l_pix, l_freq), and with an `ssim_weight` (the recipe's is 0.25) a third term ssim_weight * ssim_loss."""
+def losses(output, gt, fft_weight=0.1, ssim_weight=None, fft_backend=None):
+    """(l_pix, l_freq), and with an `ssim_weight` (the recipe's is 0.25) a third term ssim_weight * ssim_loss.  `fft_backend`:
+    fft_l1's `backend`."""
     if ssim_weight is None:
-        return l1(output, gt), fft_weight * fft_l1(output, gt)
-    return l1(output, gt), fft_weight * fft_l1(output, gt), ssim_weight * ssim_loss(output, gt)
+        return l1(output, gt), fft_weight * fft_l1(output, gt, fft_backend)
+    return l1(output, gt), fft_weight * fft_l1(output, gt, fft_backend), ssim_weight * ssim_loss(output, gt)
 
 
 _LOSS_NAMES = ("l_pix", "l_freq", "l_ssim")
@@ -198,19 +210,20 @@ def _guard_grads(params):
     return [p.grad for p in params if p.grad is not None]
 
 
-def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None, fft_weight=0.1, guard=None):
+def train_step(net, optimizer, lq, gt, as_float=True, ssim_weight=None, fft_weight=0.1, guard=None, fft_backend=None):
     """One optimize_parameters(): zero_grad, forward, L1 + 0.1*FFT (+ ssim_weight * (1 - SSIM) where a weight is given; the
     loss dict then has "l_ssim", weighted like l_freq), backward (DDP all-reduce), step.
     Returns the reduced losses {name: python float} like the reference's `reduce_loss_dict` (base_model.py:376-401: a log dict
     of floats - callers format / json-dump it).  as_float=False returns 0-dim DEVICE tensors instead: nothing in the step then
     waits for the GPU (a `float()` is a host synchronisation per iteration, under DDP on every rank); `loss_values()` converts
     such a result when it is time to log (the reference logs every `print_freq` iterations).  bench.py and the tools time the
-    step with as_float=False.  `fft_weight`: the recipe's fft_opt.loss_weight (train_wavemamba_uhdll.yml:102-104).
+    step with as_float=False.  `fft_weight`: the recipe's fft_opt.loss_weight (train_wavemamba_uhdll.yml:102-104); `fft_backend`:
+    which code computes that term (fft_l1's `backend`; None: the process default).
     `guard`: a GradGuard - after backward() it judges the parameters' gradients (the table of their addresses is rebuilt per
     call: eager gradients move), then the step is clipped or skipped as the guard says; the loss dict keeps its keys."""
     optimizer.zero_grad(set_to_none=True)
     out = net(lq)
-    terms = losses(out, gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
+    terms = losses(out, gt, fft_weight=fft_weight, ssim_weight=ssim_weight, fft_backend=fft_backend)
     _total(terms).backward()
     if guard is None or guard.attach(optimizer).run(_guard_grads([p for g in optimizer.param_groups for p in g["params"]])):
         optimizer.step()
@@ -230,9 +243,9 @@ class GraphedTrainStep:
         step = GraphedTrainStep(net, optimizer, lq0, gt0)          # 3 eager warm-up steps on (lq0, gt0), then the capture
         losses = step(lq, gt)                                      # copies the batch into the graph's input buffers, replays
     Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`) as 0-dim device tensors of the step just replayed
-    (loss_values() to log them)."""
+    (loss_values() to log them).  `fft_backend`: as in train_step; the captured graph keeps the backend it was captured with."""
 
-    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1, guard=None):
+    def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1, guard=None, fft_backend=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep: single-process training only (under torch.distributed: GraphedDDPTrainStep)")
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
@@ -246,7 +259,8 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(lq.device))
         with torch.cuda.stream(side):                              # warm-up off the capture's stream (allocator pools, library set-up)
             for _ in range(warmup):
-                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight, fft_weight=fft_weight, guard=guard)
+                train_step(net, optimizer, self.lq, self.gt, as_float=False, ssim_weight=ssim_weight, fft_weight=fft_weight, guard=guard,
+                           fft_backend=fft_backend)
         torch.cuda.current_stream(lq.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
@@ -273,7 +287,7 @@ class GraphedTrainStep:
             mode = {"capture_error_mode": "thread_local"}
         with torch.cuda.graph(self.graph, **mode):
             out = net(self.lq)
-            terms = losses(out, self.gt, fft_weight=fft_weight, ssim_weight=ssim_weight)
+            terms = losses(out, self.gt, fft_weight=fft_weight, ssim_weight=ssim_weight, fft_backend=fft_backend)
             _total(terms).backward()
             if guard is not None:
                 torch._foreach_copy_(views, [p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
@@ -318,12 +332,12 @@ class GraphedDDPTrainStep:
                     kernels and capture like any other launch)
     `capture=False` runs the same three phases eagerly - what the CPU / gloo tests exercise, and the cross-check of the replays.
     Fixed batch shape; `optimizer` as for GraphedTrainStep on a GPU.  `ssim_weight`: the weighted SSIM term joins the sum and
-    rides in the buffer as a third loss; `fft_weight`: the recipe's fft_opt.loss_weight, as in GraphedTrainStep.  Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`): 0-dim tensors holding the
+    rides in the buffer as a third loss; `fft_weight`, `fft_backend`: the recipe's fft_opt.loss_weight and the code behind that term, as in GraphedTrainStep.  Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`): 0-dim tensors holding the
     MEAN over ranks of the step just run (every rank has them - they ride in the gradient buffer; the reference's
     reduce_loss_dict, base_model.py:376-401, leaves them on rank 0 only)."""
 
     def __init__(self, net, optimizer, lq, gt, warmup=3, process_group=None, capture=True, collective="split", ssim_weight=None,
-                 fft_weight=0.1, guard=None):
+                 fft_weight=0.1, guard=None, fft_backend=None):
         if isinstance(net, (torch.nn.parallel.DistributedDataParallel, torch.nn.DataParallel)):
             raise RuntimeError("GraphedDDPTrainStep: pass the bare module, not its DistributedDataParallel wrap")
         if not (dist.is_available() and dist.is_initialized()):
@@ -333,7 +347,7 @@ class GraphedDDPTrainStep:
         self.group = process_group
         self.world = dist.get_world_size(process_group)
         self.net, self.optimizer, self.capture, self.collective = net, optimizer, capture, collective
-        self.ssim_weight, self.fft_weight = ssim_weight, fft_weight
+        self.ssim_weight, self.fft_weight, self.fft_backend = ssim_weight, fft_weight, fft_backend
         self.params = [p for g in optimizer.param_groups for p in g["params"]]
         if capture:
             if not all(p.is_cuda for p in self.params):
@@ -392,7 +406,7 @@ class GraphedDDPTrainStep:
         for p in self.params:
             p.grad = None
         out = self.net(self.lq)
-        terms = losses(out, self.gt, fft_weight=self.fft_weight, ssim_weight=self.ssim_weight)
+        terms = losses(out, self.gt, fft_weight=self.fft_weight, ssim_weight=self.ssim_weight, fft_backend=self.fft_backend)
         _total(terms).backward()
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in self.params]
         torch._foreach_copy_(self.views, grads)
