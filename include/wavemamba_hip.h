@@ -43,7 +43,7 @@ extern "C" {
 #define WM_BF16 1
 
 /* ABI version of this header (bumped on any signature change; entry points that are only ADDED - the _det forms, the channel
- * gather and wm_grad_guard - change no signature a caller compiled against 34 uses, so they do not bump it). */
+ * gather, wm_grad_guard and wm_adamw_step - change no signature a caller compiled against 34 uses, so they do not bump it). */
 int wm_abi_version(void);
 /* Identity of the sources this binary was compiled from: the first 16 hex digits of a sha256 over csrc/ and this header
  * (wave_mamba_amd/build.py passes it as -DWM_BUILD_ID; "unknown" for a bare hipcc build).  Measurements that describe
@@ -695,6 +695,31 @@ int wm_channel_gather_bwd(const float* gy, const int* index, float* gx, int B, i
 size_t wm_grad_guard_workspace_bytes(int64_t n_rows);
 int wm_grad_guard(const void* table, int64_t n_rows, float max_norm, float* record, int64_t* skipped, void* ws, size_t ws_bytes,
                   void* stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Table-driven AdamW step with the weights' exponential moving average (csrc/adamw.hip.h): torch.optim.AdamW (amsgrad = False,
+ * maximize = False) on fp32 tensors named by a device table, and - for rows that carry an ema address - the reference's model_ema
+ * (base_model.py:85-92) in the same pass.  Nothing of a step is decided on the host, so a launch captured into a HIP graph follows
+ * a learning-rate schedule and the guard above.  (Added to ABI 34: no existing signature changes.)
+ *   table      n_rows rows of six int64 in DEVICE memory: {param, grad, exp_avg, exp_avg_sq, ema or 0, count}, each address a run of
+ *              `count` contiguous floats; the host gives a row at most 4096 floats (one workgroup of 256 per row; a longer row is
+ *              still updated correctly) and no row spans two tensors.  A row whose addresses all lie on 16-byte boundaries runs on
+ *              16-byte accesses with a scalar tail; any other row (gradient views packed back to back) element by element.
+ *   lr         one float, DEVICE.    step   one float, DEVICE: the number of steps taken; this step is t = step + 1.
+ *   hyper      five doubles in HOST memory, read before the launch: {beta1, beta2, eps, weight_decay, ema_decay}; they become
+ *              launch scalars - constants of a run, and of a captured graph.  ema_decay is used by rows with an ema address.
+ *   found_inf  one float, DEVICE, or NULL: != 0 -> nothing is written - parameters, moments, averages and `step` stay bit-equal.
+ *   grad_scale one float, DEVICE, or NULL: g = grad / grad_scale.  The divided gradient is NOT written back.
+ * Per element, every operation rounded to fp32 on its own, the scalars rounded to fp32 once from double (1 - beta^t in double):
+ *   p *= 1 - lr wd;  m = fma(1 - beta1, g - m, m);  v = v beta2 + ((1 - beta2) g) g;
+ *   p += (-(lr / (1 - beta1^t)) m) / (sqrt(v) / sqrt(1 - beta2^t) + eps);  ema = ema d + (1 - d) p
+ * Two launches: the update, then one lane's step += 1 (unless found_inf).  No atomics, no memset: bit-identical run to run.
+ * Status, by host arithmetic before any launch: WM_EINVAL n_rows < 0; n_rows == 0 is WM_OK (nothing runs); WM_ENULL table, hyper, lr
+ * or step; WM_EUNSUPPORTED n_rows >= 2^31; WM_EALIGN table not 8-byte, a float pointer not 4-byte aligned; WM_EINVAL a beta or the
+ * ema decay outside [0, 1), eps or weight_decay negative.
+ * -------------------------------------------------------------------------------------------- */
+int wm_adamw_step(const void* table, int64_t n_rows, const float* lr, float* step, const double* hyper, const float* found_inf,
+                  const float* grad_scale, void* stream);
 
 /* Host-blocking wait for `event` (a hipEvent_t recorded OUTSIDE any capture) that is legal while a stream of this
  * thread is being captured: hipEventSynchronize under a thread-local relaxed capture mode

@@ -123,6 +123,7 @@ SIGNATURES = {
     "wm_channel_gather_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
     "wm_grad_guard_workspace_bytes": (_sz, [_i64]),
     "wm_grad_guard": (_i, [_p, _i64, _c.c_float, _p, _p, _p, _sz, _p]),
+    "wm_adamw_step": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -9,6 +9,8 @@ LOLv1 / 1x3x256x256 "CPU-only PyTorch forward (plumbing, no GPU)").
                         (/root/reference/basicsr/data/paired_image_dataset.py:80-131; host form of ops.paired_patches_u8)
     grad_guard          gradient norm, non-finite flag and clipping divisor of the guarded optimizer step (no reference counterpart;
                         host form of ops.grad_guard)
+    adamw_step          torch.optim.AdamW's single-tensor update plus the reference's model_ema (base_model.py:85-92; host form of
+                        ops.adamw_step)
 
 Plain PyTorch, differentiable by autograd, written from the operators' definitions.  They are
 the implementation for CPU TENSORS and nothing else: `ops.py` selects them by the device of the input, never by the absence of
@@ -224,3 +226,29 @@ def grad_guard(tensors, max_norm=None):
     if max_norm is not None and 0.0 < float(max_norm) < float("inf") and not found:
         scale = torch.clamp((norm + torch.tensor(1e-6, dtype=torch.float32)) / torch.tensor(float(max_norm), dtype=torch.float32), min=1.0)
     return torch.stack([norm, torch.tensor(1.0 if found else 0.0), scale, torch.zeros(())])
+
+
+def adamw_step(params, grads, exp_avgs, exp_avg_sqs, lr, step, betas, eps, weight_decay, emas=None, ema_decay=None, grad_scale=None):
+    """One step of ops.adamw_step / wm_adamw_step in plain PyTorch, in place: torch.optim.AdamW (amsgrad=False, maximize=False)
+    written with the tensor operations of torch's single-tensor form - with a float lr it equals torch.optim.AdamW bit for bit in
+    parameters and both moments - then, for a parameter with an entry in `emas`, the reference's model_ema (base_model.py:85-92)
+    on the new weights.  `step`: the number of steps taken so far (this one is t = step + 1; the caller advances its counter).
+    grad_scale: the update uses grad / grad_scale, the gradients themselves stay as they are.  A skipped step is the caller not
+    calling this.  The update of trainer.HipAdamW for CPU tensors, and the yardstick of the kernel's tests."""
+    beta1, beta2 = float(betas[0]), float(betas[1])
+    lr, t = float(lr), float(int(step) + 1)
+    bias_correction1, bias_correction2 = 1 - beta1 ** t, 1 - beta2 ** t
+    step_size = lr / bias_correction1
+    bias_correction2_sqrt = bias_correction2 ** 0.5
+    emas = [None] * len(params) if emas is None else emas
+    with torch.no_grad():
+        for p, g, m, v, e in zip(params, grads, exp_avgs, exp_avg_sqs, emas):
+            if grad_scale is not None:
+                g = g / float(grad_scale)
+            p.mul_(1 - lr * weight_decay)
+            m.lerp_(g, 1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            denom = (v.sqrt() / bias_correction2_sqrt).add_(eps)
+            p.addcdiv_(m, denom, value=-step_size)
+            if e is not None:
+                e.mul_(ema_decay).add_(p, alpha=1 - ema_decay)

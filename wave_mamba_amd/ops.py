@@ -12,6 +12,7 @@ Every op is a torch.autograd.Function over the C ABI of libwavemamba_hip.so (han
 gfx950).  PyTorch only supplies device memory, the current stream and autograd plumbing.  There is
 NO CPU / eager fallback: a non-CUDA tensor or a missing library raises.
 """
+import ctypes
 import os
 import weakref
 
@@ -1778,7 +1779,7 @@ GRAD_GUARD_CHUNK = 4096                    # csrc/grad_guard.hip.h: kGuardChunk 
 
 
 class _GuardTableUpload:
-    """The two pinned slots (an event each) behind grad_guard_table, per device: PairedPatchBatcher's discipline - the host rewrites
+    """The two pinned slots (an event each) behind grad_guard_table and adamw_table, per device: PairedPatchBatcher's discipline - the host rewrites
     a slot only after the copy out of it has finished, so building the next step's table does not wait for this step's copy."""
 
     def __init__(self):
@@ -1789,12 +1790,14 @@ class _GuardTableUpload:
         self.slot ^= 1
         if self.copied[slot] is not None:
             self.copied[slot].synchronize()                        # the last copy out of this pinned slot
+        width = len(rows[0])                                       # int64 words per row: 2 (grad_guard_table), 6 (adamw_table)
+        words = len(rows) * width
         pin = self.pin[slot]
-        if pin is None or pin.shape[0] < len(rows):
-            pin = self.pin[slot] = torch.empty((max(len(rows), 1024), 2), dtype=torch.int64, pin_memory=True)
-        pin.numpy()[:len(rows)] = rows
-        table = torch.empty((len(rows), 2), dtype=torch.int64, device=dev)
-        table.copy_(pin[:len(rows)], non_blocking=True)
+        if pin is None or pin.numel() < words:
+            pin = self.pin[slot] = torch.empty(max(words, 2048), dtype=torch.int64, pin_memory=True)
+        pin.numpy()[:words].reshape(len(rows), width)[:] = rows
+        table = torch.empty((len(rows), width), dtype=torch.int64, device=dev)
+        table.copy_(pin[:words].view(len(rows), width), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
         self.copied[slot] = ev
@@ -1868,7 +1871,68 @@ def grad_guard(tensors_or_table, max_norm=None, record=None, skipped=None, works
     return record, counter
 
 
-SSIM_TILE_H, SSIM_TILE_W = 24, 32          # csrc/ssim_loss.hip.h: SL_TH x SL_TW, one workgroup per tile (the tests' edge shapes)
+ADAMW_ROW_WORDS = 6                        # csrc/adamw.hip.h: kAdamwRowWords - {param, grad, exp_avg, exp_avg_sq, ema or 0, count}
+
+
+def adamw_table(params, grads, exp_avgs, exp_avg_sqs, emas=None):
+    """The device table wm_adamw_step reads: for every parameter rows {param, grad, exp_avg, exp_avg_sq, ema or 0, count} of at most
+    GRAD_GUARD_CHUNK floats (a tensor of more is split, an empty one gives no row; no row spans two tensors).  All five lists run
+    in parallel over contiguous float32 CUDA tensors of one device, each quintuple of one size; `emas` is None (no averages) or
+    holds None for a parameter that keeps none.  -> (table (n_rows, 6) int64 on the device, n_rows).  Like grad_guard_table the
+    table is built OUTSIDE a graph capture, holds raw addresses - the caller keeps every tensor alive and in place - and must
+    itself outlive a graph that captured a launch on it."""
+    params, grads, exp_avgs, exp_avg_sqs = list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)
+    emas = [None] * len(params) if emas is None else list(emas)
+    if not len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(emas):
+        raise ValueError("adamw_table: the lists differ in length")
+    tensors = [t for group in (params, grads, exp_avgs, exp_avg_sqs, emas) for t in group if t is not None]
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            what = f"{t.dtype} on {t.device}, contiguous: {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"adamw_table: contiguous float32 CUDA tensors only, got {what}")
+    if len({t.device for t in tensors}) > 1:
+        raise ValueError("adamw_table: the tensors live on more than one device")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("adamw_table: a host-to-device copy must not be captured - build the table before the capture")
+    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    rows = []
+    for p, g, m, v, e in zip(params, grads, exp_avgs, exp_avg_sqs, emas):
+        n = p.numel()
+        if any(t.numel() != n for t in (g, m, v) + (() if e is None else (e,))):
+            raise ValueError(f"adamw_table: a parameter of {n} floats with a gradient, moment or average of another size")
+        bases = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr())
+        eb = 0 if e is None else e.data_ptr()
+        for at in range(0, n, GRAD_GUARD_CHUNK):
+            rows.append(tuple(b + 4 * at for b in bases) + (eb + 4 * at if eb else 0, min(GRAD_GUARD_CHUNK, n - at)))
+    if not rows:
+        return torch.empty((0, ADAMW_ROW_WORDS), dtype=torch.int64, device=dev), 0
+    up = _GUARD_UPLOADS.setdefault(dev.index, _GuardTableUpload())
+    return up.upload(rows, dev), len(rows)
+
+
+def adamw_step(table, lr, step, betas, eps, weight_decay, ema_decay=None, found_inf=None, grad_scale=None):
+    """One AdamW step (torch.optim.AdamW, amsgrad=False, maximize=False) over the (table, n_rows) pair of adamw_table, with the
+    moving average ema = d ema + (1 - d) p of the new weights for the rows that carry an ema address (wm_adamw_step: two launches,
+    no atomics, no memset, no host read - bit-identical run to run and capturable).
+    lr: one float32 on the device (a scheduler fills it in place); step: one float32 on the device, the steps taken so far, advanced
+    by one here; betas, eps, weight_decay, ema_decay: Python floats - launch scalars, constants of a captured graph (a table built
+    with `emas` needs an ema_decay: the table is not read back here to check).  found_inf /
+    grad_scale: one float32 each on the device (GradGuard's record) or None: with found_inf != 0 nothing is written, the counter
+    included; with grad_scale the update uses grad / grad_scale - the division is NOT written back: p.grad keeps the unclipped
+    values (torch's fused AdamW stores them).  cpu_twin.adamw_step states the same update in plain PyTorch."""
+    table, n_rows = table
+    _require_cuda("adamw_step", table, lr, step, found_inf, grad_scale)
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < ADAMW_ROW_WORDS * n_rows:
+        raise ValueError("adamw_step: the table is (n_rows, 6) int64, contiguous")
+    for name, t in (("lr", lr), ("step", step), ("found_inf", found_inf), ("grad_scale", grad_scale)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1):
+            raise ValueError(f"adamw_step: {name} is one float32 on the device")
+    hyper = (ctypes.c_double * 5)(float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                  0.0 if ema_decay is None else float(ema_decay))
+    _launch(table.device, "wm_adamw_step", table if n_rows else None, n_rows, lr, step, hyper, found_inf, grad_scale)
+
+
+SSIM_TILE_H, SSIM_TILE_W = 24, 32         # csrc/ssim_loss.hip.h: SL_TH x SL_TW, one workgroup per tile (the tests' edge shapes)
 
 
 def _ssim_forward(a, b, want_a, want_b):

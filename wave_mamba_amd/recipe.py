@@ -36,6 +36,17 @@ Every print_freq line then carries `grad_norm` (the last step's) and `skipped_st
 are not finite leaves weights and optimizer state as they are while the iteration and the lr schedule advance (the batch was
 consumed); the training state carries `skipped_steps` beside the batch position (a state without it resumes at 0).
 
+The optimizer's backend and the weights' moving average.  Two optional keys (absent: nothing changes, the files included):
+    train:
+      ema_decay: 0.999       # standard BasicSR; 0 or absent: off; needs the backend below
+      optim_g:
+        backend: hip         # trainer.HipAdamW: the table-driven HIP step; torch (default): torch's fused AdamW
+With an ema_decay the optimizer's kernel keeps the reference's model_ema (base_model.py:85-92) in its own pass.  The average starts
+at the weights the run starts from (after pretrained weights are loaded and rank 0's broadcast), the graphed constructor's warm-up
+is undone for it as for the moments, every net_g_*.pth carries `params_ema` beside `params`, validation scores the averaged
+weights (swapped in and out in place, as BasicSR validates with net_g_ema) and a resumed run takes the average from the weights
+file's `params_ema`, so it continues exactly.
+
 Graphed mode and "one loop iteration = one recipe iteration".  GraphedTrainStep's constructor runs three warm-up steps on a side
 stream before it captures; they are real optimizer steps.  The loop saves weights, moments and step counters before the
 constructor and restores them IN PLACE after it (the graph reads those very tensors), so the warm-up leaves no trace and every
@@ -54,7 +65,7 @@ from .data import DeviceImageStore, PairedPatchBatcher
 from .registry import build_network
 
 LOG = logging.getLogger("wave_mamba_amd")
-_OPTIM_KEYS = ("type", "lr", "weight_decay", "betas")
+_OPTIM_KEYS = ("type", "lr", "weight_decay", "betas", "backend")
 _GUARD_KEYS = ("max_norm", "skip_nonfinite")
 
 
@@ -118,6 +129,26 @@ def fft_backend_option(opt):
     return backend
 
 
+def optimizer_backend_options(opt):
+    """(train.optim_g.backend, train.ema_decay) -> (backend, ema_decay) for trainer.make_optimizer.  backend: `torch` (also when
+    absent) or `hip` - trainer.HipAdamW.  train.ema_decay (standard BasicSR): 0 or absent for off -> None; otherwise a number in
+    [0, 1), and it needs backend: hip - the average is kept by that optimizer's kernel.  A ValueError names the key."""
+    backend = _get(opt, "train.optim_g.backend", "torch")
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"train.optim_g.backend: {backend!r} is not one of torch, hip")
+    decay = _get(opt, "train.ema_decay")
+    if decay is None:
+        return backend, None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f"train.ema_decay: {decay!r} is not a number in [0, 1) (0 or absent: no moving average)")
+    if float(decay) == 0.0:
+        return backend, None
+    if backend != "hip":
+        raise ValueError(f"train.ema_decay: {decay!r} needs train.optim_g.backend: hip (the moving average is kept by "
+                         "trainer.HipAdamW's kernel)")
+    return backend, float(decay)
+
+
 def check_options(opt):
     """Refuse up front what the loop cannot do; every ValueError names the offending key."""
     if opt.get("scale", 1) != 1:
@@ -136,6 +167,7 @@ def check_options(opt):
             raise ValueError(f"{key}: missing")
     guard_options(opt)
     fft_backend_option(opt)
+    optimizer_backend_options(opt)
     metrics = usable_metrics(opt)
     key_metric = _get(opt, "val.key_metric")
     if opt.get("val") is not None and key_metric is not None and key_metric not in metrics:
@@ -299,8 +331,10 @@ class Trainer:
         pretrained = _get(opt, "path.pretrain_network_g")
         resume_state = _get(opt, "path.resume_state")
         optim = tr["optim_g"]
+        backend, self.ema_decay = optimizer_backend_options(opt)
         self.optimizer = trainer.make_optimizer(self.net, lr=float(optim["lr"]), weight_decay=float(optim.get("weight_decay", 1e-2)),
-                                                betas=tuple(optim.get("betas", (0.9, 0.999))), capturable=self.graphed)
+                                                betas=tuple(optim.get("betas", (0.9, 0.999))), capturable=self.graphed,
+                                                backend=backend, ema_decay=self.ema_decay)
         schedulers.set_lr(self.optimizer, [float(optim["lr"])] * len(self.optimizer.param_groups))   # the exact float64 base lr
         self.scheduler = schedulers.build_scheduler(self.optimizer, tr["scheduler"])
         guard = guard_options(opt)
@@ -322,6 +356,7 @@ class Trainer:
                       logging.WARNING)
         self.current_iter, self.epoch, self._pos, self._finished = 0, 0, 0, False
         self._gstep = self._run_graphed = None
+        self._ema_loaded = False
 
         if resume_state:                                           # before anything is captured
             self._resume(resume_state, pretrained)
@@ -329,6 +364,8 @@ class Trainer:
             trainer.load_network(self.net, pretrained, strict=bool(_get(opt, "path.strict_load", True)))
         if self.distributed:                                       # seeds differ by rank: rank 0's initialisation is the run's
             trainer.broadcast_parameters(self.net, self.group)
+        if self.ema_decay is not None and not self._ema_loaded:    # the average starts at the weights the run starts from
+            self.optimizer.reset_ema()
 
     # -- resume ---------------------------------------------------------------------------------------------------------------------
     def _resume(self, path, pretrained):
@@ -343,6 +380,11 @@ class Trainer:
         epoch, current_iter = trainer.resume_training(state, [self.optimizer], [self.scheduler])
         weights = pretrained or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(path))), "models", f"net_g_{current_iter}.pth")
         trainer.load_network(self.net, weights, strict=bool(_get(self.opt, "path.strict_load", True)) if pretrained else True)
+        if self.ema_decay is not None:                             # the average continues from the file's params_ema where it has one
+            blob = torch.load(weights, map_location="cpu", weights_only=True)
+            if isinstance(blob, dict) and "params_ema" in blob:
+                self.optimizer.load_ema(blob["params_ema"], self.net)
+                self._ema_loaded = True
         self.epoch, self.current_iter = int(epoch), int(current_iter)
         extra = state.get("recipe")
         if self.guard is not None:                                 # (a state without the count, or one the reference wrote: 0)
@@ -367,8 +409,9 @@ class Trainer:
         return os.path.join(self.out_dir, "models", f"net_g_{label}.pth")
 
     def _save_network(self, label, current_iter, epoch):
-        if self.writer:
-            trainer.save_network(self.net, self._model_path(label), current_iter, epoch)
+        if self.writer:                                            # with train.ema_decay the file carries params and params_ema
+            ema = None if self.ema_decay is None else self.optimizer.ema_state_dict(self.net)
+            trainer.save_network(self.net, self._model_path(label), current_iter, epoch, ema=ema)
 
     def _all_rng_states(self):
         """Every rank's batcher random state, on every rank: each rank fills its row of a (world, 624 + 1) int64 matrix and one
@@ -411,6 +454,7 @@ class Trainer:
         weights = {k: v.detach().clone() for k, v in self.net.state_dict().items()}
         moments = {p: {k: v.clone() for k, v in st.items() if isinstance(v, torch.Tensor)} for p, st in self.optimizer.state.items()}
         skipped = None if self.guard is None else int(self.guard.skipped)         # the warm-up steps are guarded steps too
+        emas = [a.clone() for a in self.optimizer.ema_arenas()] if self.ema_decay is not None else []   # ... and averaged ones
         if self.distributed:
             step = trainer.GraphedDDPTrainStep(self.net, self.optimizer, lq, gt, process_group=self.group, capture=self.graphed,
                                                collective=self.collective, ssim_weight=self.ssim_weight, fft_weight=self.fft_weight,
@@ -428,6 +472,8 @@ class Trainer:
                 for k, v in self.optimizer.state.get(p, {}).items():
                     if isinstance(v, torch.Tensor):
                         v.copy_(saved[k]) if saved is not None else v.zero_()    # no state before: exp_avg, exp_avg_sq, step = 0
+            for a, saved in zip(self.optimizer.ema_arenas() if emas else [], emas):
+                a.copy_(saved)                                     # the average is put back, never zeroed
         return step
 
     def _step(self, rows):
@@ -488,7 +534,13 @@ class Trainer:
 
     def validate(self, current_iter, epoch):
         """One validation: scores, best bookkeeping, the best checkpoint, one log line.  -> the result dict."""
-        results = self.score()
+        if self.ema_decay is not None:                             # the averaged weights are scored, as BasicSR does: swapped in
+            self.optimizer.swap_ema()                              # and out again in place (addresses, tables and graphs stay)
+        try:
+            results = self.score()
+        finally:
+            if self.ema_decay is not None:
+                self.optimizer.swap_ema()
         if self.best.update(results, current_iter, self.key_metric):
             self._save_network(f"best_{current_iter}" if self.key_metric is not None else "best_", current_iter, epoch)
         self._log({"iter": current_iter, "epoch": epoch, "validation": results,

@@ -87,20 +87,271 @@ def _total(terms):
     return total.mean()
 
 
-def make_optimizer(net, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.99), capturable=False):
+def make_optimizer(net, lr=5e-4, weight_decay=1e-3, betas=(0.9, 0.99), capturable=False, backend="torch", ema_decay=None):
     """AdamW as the reference configures it (train_wavemamba_uhdll.yml:75-79).  On a GPU the 591 small tensors are
     updated by the fused multi-tensor implementation (one launch per ~hundred tensors instead of ~10 per tensor
     group); same arithmetic.  capturable: step counters AND the learning rate on the device, for GraphedTrainStep - a
     Python-float lr would be baked into the captured AdamW launch as a kernel scalar and a scheduler (the reference's recipe
     uses CosineAnnealingRestartCyclicLR, train_wavemamba_uhdll.yml:86-90: schedulers.py) would change nothing in the replays;
     schedulers.py and torch's own schedulers `fill_()` a tensor lr in place, which the replayed kernel reads (a warm-up or any
-    other direct change goes through schedulers.set_lr, never `group["lr"] = value`)."""
+    other direct change goes through schedulers.set_lr, never `group["lr"] = value`).
+    backend: "torch" (the default: everything above, and every call launches what it always launched) or "hip" - HipAdamW, this
+    package's table-driven kernel, always capturable on a GPU.  ema_decay (backend "hip" only): keep an exponential moving average
+    of the weights inside the optimizer's kernel (HipAdamW)."""
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"make_optimizer: backend {backend!r} is not one of ('torch', 'hip')")
     params = [p for p in net.parameters() if p.requires_grad]
+    if backend == "hip":
+        return HipAdamW(params, lr=lr, weight_decay=weight_decay, betas=betas, ema_decay=ema_decay)
+    if ema_decay is not None:
+        raise ValueError("make_optimizer: ema_decay needs backend='hip' (the average is kept by HipAdamW's kernel)")
     fused = bool(params) and all(p.is_cuda for p in params)
     kw = {"capturable": True} if capturable else {}
     if capturable and fused:
         lr = torch.tensor(float(lr), dtype=torch.float32, device=params[0].device)
     return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay, betas=betas, fused=fused, **kw)
+
+
+class _AdamwGroup:
+    """One param group's device state behind HipAdamW: three flat fp32 arenas (every tensor's slot starts on a 16-byte boundary),
+    the per-parameter views of them, the step counter and the tables of addresses built so far."""
+
+    def __init__(self, params, with_ema):
+        self.params = params
+        self.device = params[0].device
+        sizes = [p.numel() for p in params]
+        slots = [(n + 3) // 4 * 4 for n in sizes]
+        self.sizes, self.slots = sizes, slots
+        self.exp_avg, self.exp_avg_sq = self.arena(), self.arena()
+        self.ema = self.arena() if with_ema else None
+        self.m, self.v = self.views(self.exp_avg), self.views(self.exp_avg_sq)
+        self.e = self.views(self.ema) if with_ema else None
+        self.scratch = None                                        # swap_ema's, allocated at the first swap
+        self.step = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.eager = (None, None)                                  # (gradient addresses, table): rebuilt when a gradient moved
+        self.kept = {}                                             # gradient addresses -> table, for prepared and captured launches
+
+    def arena(self):
+        return torch.zeros(sum(self.slots), dtype=torch.float32, device=self.device)
+
+    def views(self, flat):
+        return [v[:n].view_as(p) for v, n, p in zip(flat.split(self.slots), self.sizes, self.params)]
+
+
+class HipAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW (amsgrad=False, maximize=False: both refused) whose step is this package's HIP kernel, with an optional
+    exponential moving average of the weights computed in the same pass (the reference's model_ema, base_model.py:85-92;
+    train.ema_decay of a BasicSR recipe).
+
+        optimizer = HipAdamW(params, lr=5e-4, betas=(0.9, 0.99), weight_decay=1e-3, ema_decay=0.999)      # or make_optimizer(backend="hip")
+        ... optimizer.step() ...; optimizer.swap_ema(); validate(net); optimizer.swap_ema(); optimizer.ema_state_dict(net)
+
+    On a GPU one step is ops.adamw_step per param group (the recipe has one): a launch over a device table of addresses
+    {param, grad, exp_avg, exp_avg_sq, ema}, one workgroup per 4096 floats, plus one lane's counter increment.  The learning rate
+    is a device tensor (schedulers.set_lr and the schedulers fill it in place) and the step counter is ONE float32 on the device, so
+    the step is always capturable.  `found_inf` / `grad_scale` attributes (GradGuard.attach sets them) are read on the device: a step
+    with found_inf set writes nothing, the counter included; with grad_scale the update uses grad / grad_scale, and - unlike
+    torch's fused kernel - the divided gradients are NOT written back: p.grad keeps the unclipped values.
+    exp_avg, exp_avg_sq and the average live in three flat fp32 arenas (every tensor's slot on a 16-byte boundary), all created
+    here: moments and counter at 0, the average a copy of the weights.  The table is rebuilt when a gradient's address changed
+    (eager steps); a captured step needs it before the capture: prepare(grads) with the tensors that will be p.grad (GraphedTrainStep
+    and GraphedDDPTrainStep do that).  Parameters whose .grad is None are skipped.  CPU parameters (the gloo tests) run
+    cpu_twin.adamw_step with a float lr: torch.optim.AdamW's single-tensor arithmetic, bit for bit.
+    state_dict() has torch AdamW's keys - per parameter `step`, `exp_avg`, `exp_avg_sq`, and its group keys - so a training state
+    written with either backend resumes with the other; load_state_dict copies INTO the arenas (the table holds their addresses) and
+    refuses per-parameter `step` values that differ from each other.  The average is no part of that dict: ema_state_dict(net) /
+    load_ema(state, net) / reset_ema() / swap_ema(), all in place."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False, ema_decay=None):
+        if amsgrad or maximize:
+            raise ValueError("HipAdamW: amsgrad and maximize are not implemented")
+        if isinstance(lr, torch.Tensor):
+            lr = float(lr)
+        if not (0.0 <= lr and 0.0 <= eps and 0.0 <= weight_decay and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"HipAdamW: lr {lr!r}, betas {betas!r}, eps {eps!r}, weight_decay {weight_decay!r}")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"HipAdamW: ema_decay {ema_decay!r} does not lie in [0, 1)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        defaults = dict(torch.optim.AdamW([torch.zeros(1)]).defaults)         # torch AdamW's group keys, whatever the torch version
+        defaults.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
+                        amsgrad=False, maximize=False, foreach=None, capturable=True, differentiable=False, fused=None)
+        self._groups = None
+        super().__init__(params, defaults)
+        self._groups = []
+        for group in self.param_groups:
+            ps = group["params"]
+            if not ps:
+                raise ValueError("HipAdamW: a param group without parameters")
+            if not all(p.dtype == torch.float32 and p.is_contiguous() and p.device == ps[0].device for p in ps):
+                raise ValueError("HipAdamW: contiguous float32 parameters on one device per group")
+            st = _AdamwGroup(ps, self.ema_decay is not None)
+            self._groups.append(st)
+            group["capturable"] = st.device.type == "cuda"       # (what a torch AdamW that loads this state will be told)
+            if st.device.type == "cuda":
+                group["lr"] = torch.tensor(float(group["lr"]), dtype=torch.float32, device=st.device)
+            for p, m, v in zip(ps, st.m, st.v):
+                self.state[p] = {"step": st.step.view(()), "exp_avg": m, "exp_avg_sq": v}
+        self.reset_ema()
+
+    def add_param_group(self, param_group):
+        if self._groups is not None:
+            raise RuntimeError("HipAdamW: param groups are fixed at construction (the arenas and tables are laid out there)")
+        super().add_param_group(param_group)
+
+    # -- the step ---------------------------------------------------------------------------------------------------------------
+    def _build(self, st, grads):
+        from . import ops
+        rows = [(p, g, m, v, e) for p, g, m, v, e in zip(st.params, grads, st.m, st.v, st.e or [None] * len(st.params)) if g is not None]
+        return ops.adamw_table(*[list(col) for col in zip(*rows)]) if rows else ops.adamw_table([], [], [], [])
+
+    @staticmethod
+    def _key(grads):
+        return tuple(0 if g is None else g.data_ptr() for g in grads)
+
+    def prepare(self, grads, group=0):
+        """Build and keep the table for gradients at the addresses of `grads` (parallel to the group's parameters; None: no
+        gradient) - outside a capture, for a step that will run inside one with exactly these tensors as p.grad."""
+        st = self._groups[group]
+        if st.device.type == "cuda":
+            st.kept[self._key(grads)] = self._build(st, list(grads))
+
+    def _table(self, st):
+        grads = [p.grad for p in st.params]
+        key = self._key(grads)
+        capturing = torch.cuda.is_current_stream_capturing()
+        table = st.kept.get(key)
+        if table is None and st.eager[0] == key:
+            table = st.eager[1]
+            if capturing:
+                st.kept[key] = table                               # a captured launch holds the table's address: never dropped
+        if table is None:
+            if capturing:
+                raise RuntimeError("HipAdamW: no table for these gradient addresses - call prepare(grads) before the capture")
+            table = self._build(st, grads)
+            st.eager = (key, table)
+        return table
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        found_inf, grad_scale = getattr(self, "found_inf", None), getattr(self, "grad_scale", None)
+        for group, st in zip(self.param_groups, self._groups):
+            if all(p.grad is None for p in st.params):
+                continue
+            if st.device.type == "cuda":
+                from . import ops
+                ops.adamw_step(self._table(st), group["lr"], st.step, group["betas"], group["eps"], group["weight_decay"],
+                               self.ema_decay, found_inf, grad_scale)
+                ops.conv2d_cache_clear()                           # the kernel writes through raw addresses: no `_version` moves
+                continue
+            if found_inf is not None and float(found_inf):
+                continue
+            from . import cpu_twin
+            have = [i for i, p in enumerate(st.params) if p.grad is not None]
+            cpu_twin.adamw_step([st.params[i] for i in have], [st.params[i].grad for i in have], [st.m[i] for i in have],
+                                [st.v[i] for i in have], float(group["lr"]), int(st.step), group["betas"], group["eps"],
+                                group["weight_decay"], None if st.e is None else [st.e[i] for i in have], self.ema_decay,
+                                None if grad_scale is None else float(grad_scale))
+            st.step += 1
+        return loss
+
+    # -- checkpoints ------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        state = super().state_dict()
+        state["state"] = {k: {n: (t.detach().clone() if isinstance(t, torch.Tensor) else t) for n, t in s.items()}
+                          for k, s in state["state"].items()}
+        for g in state["param_groups"]:
+            if isinstance(g["lr"], torch.Tensor):
+                g["lr"] = g["lr"].detach().clone()
+        return state
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups):
+            raise ValueError("HipAdamW.load_state_dict: the number of param groups differs")
+        for group, sg, st in zip(self.param_groups, saved, self._groups):
+            if len(sg["params"]) != len(st.params):
+                raise ValueError("HipAdamW.load_state_dict: a param group's size differs")
+            if sg.get("amsgrad", False) or sg.get("maximize", False):
+                raise ValueError("HipAdamW.load_state_dict: a state with amsgrad or maximize")
+            states = [state_dict["state"].get(i) for i in sg["params"]]
+            steps = sorted({float(s["step"]) for s in states if s is not None})
+            if len(steps) > 1:
+                raise ValueError(f"HipAdamW.load_state_dict: the parameters' step counts differ ({steps[0]:g} .. {steps[-1]:g}); "
+                                 "this optimizer keeps one counter")
+            for m, v, s in zip(st.m, st.v, states):
+                if s is None:                                      # torch keeps no state for a parameter that never had a gradient
+                    m.zero_()
+                    v.zero_()
+                else:
+                    m.copy_(s["exp_avg"])
+                    v.copy_(s["exp_avg_sq"])
+            st.step.fill_(steps[0] if steps else 0.0)
+            for k, value in sg.items():
+                if k == "lr":
+                    if isinstance(group["lr"], torch.Tensor):
+                        group["lr"].fill_(float(value))
+                    else:
+                        group["lr"] = float(value)
+                elif k == "betas":
+                    group[k] = (float(value[0]), float(value[1]))
+                elif k in ("eps", "weight_decay") or k not in self.defaults and k != "params":
+                    group[k] = value                               # (initial_lr, lr_host: the schedulers' entries travel here)
+
+    # -- the moving average -----------------------------------------------------------------------------------------------------
+    def _need_ema(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError(f"HipAdamW.{what}: no moving average is kept (ema_decay=None)")
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """The average becomes a copy of the current weights, in place (no-op without an ema_decay)."""
+        for st in self._groups or []:
+            if st.e is not None:
+                torch._foreach_copy_(st.e, [p.detach() for p in st.params])
+
+    def ema_arenas(self):
+        """The flat tensors that hold the averages, one per param group (to snapshot and restore them in place)."""
+        return [st.ema for st in self._groups if st.ema is not None]
+
+    def ema_state_dict(self, net):
+        """net.state_dict() with every parameter this optimizer updates taken from the average; buffers and frozen parameters come
+        from the network.  Clones: the result does not follow later steps."""
+        self._need_ema("ema_state_dict")
+        net = _bare(net)
+        state = {k: v.detach().clone() for k, v in net.state_dict().items()}
+        by_param = {id(p): e for st in self._groups for p, e in zip(st.params, st.e)}
+        for name, p in net.named_parameters():
+            if id(p) in by_param and name in state:
+                state[name] = by_param[id(p)].detach().clone()
+        return state
+
+    @torch.no_grad()
+    def load_ema(self, state, net):
+        """Fill the average from a state dict of the network (a file's `params_ema`), in place; a parameter the dict lacks keeps
+        its average."""
+        self._need_ema("load_ema")
+        state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
+        by_param = {id(p): e for st in self._groups for p, e in zip(st.params, st.e)}
+        for name, p in _bare(net).named_parameters():
+            if id(p) in by_param and name in state:
+                by_param[id(p)].copy_(state[name])
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange weights and average in place, through a scratch arena: no address changes, so tables and captured graphs stay
+        valid.  Call it twice around a validation."""
+        self._need_ema("swap_ema")
+        for st in self._groups:
+            if st.scratch is None:
+                st.scratch = st.arena()
+            st.scratch.copy_(st.ema)
+            torch._foreach_copy_(st.e, [p.detach() for p in st.params])
+            torch._foreach_copy_([p.detach() for p in st.params], st.views(st.scratch))
 
 
 def wrap_ddp(net, device=None, find_unused_parameters=False, force=False):
@@ -172,9 +423,9 @@ class GradGuard:
             raise ValueError("GradGuard.attach: the optimizer has no parameters")
         self.to(params[0].device)
         if self.record.is_cuda:
-            if not all(g.get("fused", False) for g in optimizer.param_groups):
-                raise RuntimeError("GradGuard.attach: on a GPU the optimizer must be the fused AdamW (make_optimizer): only its kernel "
-                                   "reads found_inf / grad_scale from the device")
+            if not isinstance(optimizer, HipAdamW) and not all(g.get("fused", False) for g in optimizer.param_groups):
+                raise RuntimeError("GradGuard.attach: on a GPU the optimizer must be the fused AdamW (make_optimizer) or a HipAdamW: "
+                                   "only their kernels read found_inf / grad_scale from the device")
             if self.skip_nonfinite:
                 optimizer.found_inf = self.found_inf
             if self.max_norm is not None:
@@ -243,7 +494,9 @@ class GraphedTrainStep:
         step = GraphedTrainStep(net, optimizer, lq0, gt0)          # 3 eager warm-up steps on (lq0, gt0), then the capture
         losses = step(lq, gt)                                      # copies the batch into the graph's input buffers, replays
     Returns {"l_pix", "l_freq"} (and "l_ssim" with an `ssim_weight`) as 0-dim device tensors of the step just replayed
-    (loss_values() to log them).  `fft_backend`: as in train_step; the captured graph keeps the backend it was captured with."""
+    (loss_values() to log them).  `fft_backend`: as in train_step; the captured graph keeps the backend it was captured with.
+    With a HipAdamW (always capturable), as with a guard, the captured step copies its gradients into one flat buffer allocated
+    before the capture and steps on views of it: the optimizer's table of addresses is built there, outside the capture."""
 
     def __init__(self, net, optimizer, lq, gt, warmup=3, ssim_weight=None, fft_weight=0.1, guard=None, fft_backend=None):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -265,7 +518,9 @@ class GraphedTrainStep:
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
         self.guard = guard
-        if guard is not None:
+        hip_adamw = isinstance(optimizer, HipAdamW)
+        flat_grads = guard is not None or hip_adamw                # a HipAdamW's table needs gradient addresses before the capture too
+        if flat_grads:
             # the gradients of a capture live in the graph's pool; the guard's table holds addresses and its upload is a host-to-device
             # copy, so both are made HERE: one flat buffer the captured step copies its gradients into, per-parameter views of it as
             # the p.grad AdamW reads (GraphedDDPTrainStep's scheme), and one table over the whole buffer
@@ -276,9 +531,15 @@ class GraphedTrainStep:
             slots = [(n + 3) // 4 * 4 for n in sizes]
             self.flat = torch.zeros(sum(slots), dtype=torch.float32, device=lq.device)
             views = [v[:n].view_as(p) for v, n, p in zip(self.flat.split(slots), sizes, params)]
+        if guard is not None:
             guard.attach(optimizer)
             from . import ops
             self.guard_table = ops.grad_guard_table([self.flat])      # kept: the captured launch holds the table's address
+        if hip_adamw:
+            at = 0
+            for gi, g in enumerate(optimizer.param_groups):           # (the optimizer keeps its tables: one per param group)
+                optimizer.prepare(views[at:at + len(g["params"])], group=gi)
+                at += len(g["params"])
         mode = {}
         if dist.is_available() and dist.is_initialized():
             # a (one-rank) process group exists: its watchdog thread polls events while this thread captures, which the default
@@ -289,10 +550,11 @@ class GraphedTrainStep:
             out = net(self.lq)
             terms = losses(out, self.gt, fft_weight=fft_weight, ssim_weight=ssim_weight, fft_backend=fft_backend)
             _total(terms).backward()
-            if guard is not None:
+            if flat_grads:
                 torch._foreach_copy_(views, [p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
                 for p, v in zip(params, views):
                     p.grad = v
+            if guard is not None:
                 guard.run([self.flat], table=self.guard_table)
             optimizer.step()
         self.losses = {k: t.detach() for k, t in zip(_LOSS_NAMES, terms)}
@@ -374,6 +636,13 @@ class GraphedDDPTrainStep:
                 from . import ops
                 self.guard_table = ops.grad_guard_table([self.flat[:-nl]])
         self._grads = self.flat[:-nl]
+        if isinstance(optimizer, HipAdamW):
+            # its table over the packed views (most of them start off a 16-byte boundary: the kernel's element-wise rows), built
+            # once, before any capture; the warm-up and the eager form find it under the same addresses
+            at = 0
+            for gi, g in enumerate(optimizer.param_groups):
+                optimizer.prepare(self.views[at:at + len(g["params"])], group=gi)
+                at += len(g["params"])
         if not capture:
             return
         side = torch.cuda.Stream(dev)
@@ -485,13 +754,19 @@ def _atomic_save(obj, path):
     os.replace(tmp, path)
 
 
-def save_network(net, path, current_iter=-1, epoch=0, param_key="params"):
+def save_network(net, path, current_iter=-1, epoch=0, param_key="params", ema=None):
     """`{param_key: state_dict on the CPU without 'module.' prefixes, 'iter': int | 'latest', 'epoch': int}` -
-    the file layout `inference_wavemamba.py:74` / `load_network` read.  Rank 0 only (`@master_only`, :214)."""
+    the file layout `inference_wavemamba.py:74` / `load_network` read.  Rank 0 only (`@master_only`, :214).
+    `ema`: a state dict of averaged weights (HipAdamW.ema_state_dict) - written beside `params` as `params_ema`, the key the
+    reference's load_network looks for first (base_model.py:298-315) and load_network(param_key="params_ema") reads; None
+    (the default): the file is what it always was."""
     if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
         return None
-    state = {(k[7:] if k.startswith("module.") else k): v.detach().cpu() for k, v in _bare(net).state_dict().items()}
-    _atomic_save({param_key: state, "iter": "latest" if current_iter == -1 else current_iter, "epoch": epoch}, path)
+    plain = lambda sd: {(k[7:] if k.startswith("module.") else k): v.detach().cpu() for k, v in sd.items()}
+    blob = {param_key: plain(_bare(net).state_dict())}
+    if ema is not None:
+        blob["params_ema"] = plain(ema)
+    _atomic_save({**blob, "iter": "latest" if current_iter == -1 else current_iter, "epoch": epoch}, path)
     return path
 
 
