@@ -408,6 +408,30 @@ int wm_layernorm_tok_bwd(const float* x, const float* weight, const float* gy, f
 int wm_image_pre_u8(const uint8_t* image, float* out, int h, int w, int Hp, int Wp, int swap_rb, void* stream);
 int wm_image_post_u8(const float* in, uint8_t* image, int h, int w, int Hp, int Wp, int swap_rb, void* stream);
 
+/* The same I/O step for N images per launch, a dihedral mode per image and a group average on the way out, csrc/images_io.hip.h:
+ * batched, graph-replayed and self-ensembled inference.  Both are driven by DEVICE tables of int64 words (ops.images_io_table).
+ *   wm_images_pre_u8   row n = {image, h, w, mode}: a contiguous (h, w, 3) uint8 image on the device and a mode 0..7 of
+ *                      data_augmentation (the table of wm_paired_patches_u8 below; modes 2, 3, 6, 7 turn h x w into w x h).
+ *                      out[n] (3, Hp, Wp) fp32 = reflect_pad(chw(mode(image)) / 255): the padding follows the transform, bottom / right
+ *                      of the transformed image, as check_image_size(aug(img)) pads.  out is contiguous (N, 3, Hp, Wp); every row
+ *                      must give the launch's (Hp, Wp) with pads smaller than the transformed image.  swap_rb: BGR -> RGB.
+ *   wm_images_post_u8  row = {image, h, w, k, word_0 .. word_7}: a contiguous (h, w, 3) uint8 destination and k in 1..8 sources,
+ *                      word = mode | tensor << 8 | index << 16 naming image `index` of src0 (tensor 0; (N0, 3, Hp0, Wp0) fp32,
+ *                      contiguous) or of src1 (tensor 1; NULL with N1 = 0 when unused) - the result of the network on the image
+ *                      transformed by `mode`.  image = hwc(round_half_even(clamp(mean, 0, 1) * 255)), mean = (((y_0 + y_1) + ...)
+ *                      + y_{k-1}) * (1 / k) in fp32 in the row's order, y_s = source s cropped to the transformed shape and turned
+ *                      back by the inverse mode.  k = 1, mode 0 is wm_image_post_u8 bit for bit.  h_max / w_max: the largest
+ *                      destination (the grid).  swap_rb: RGB -> BGR.
+ * One launch each, no atomics, nothing zeroed first: both capture into a HIP graph, and the tables are read by the KERNELS.  The host
+ * cannot check a device table: a pre row that names no image, does not fit (Hp, Wp) or whose padding reaches the image's size
+ * yields zeros; a post row with a NULL image, k outside 1..8, a source index outside its tensor or a source smaller than the
+ * destination's transformed shape is left unwritten - neither indexes out of range.  The pointers are the caller's responsibility.
+ * WM_EINVAL: a negative size; an empty launch is a no-op; WM_EALIGN: table not 8-byte, fp32 tensors not 4-byte aligned;
+ * WM_EUNSUPPORTED: more than 65535 images / rows of the table, Hp or h_max above 65535, Wp or w_max above 65535 * 32. */
+int wm_images_pre_u8(const int64_t* table, float* out, int N, int Hp, int Wp, int swap_rb, void* stream);
+int wm_images_post_u8(const int64_t* table, const float* src0, int N0, int Hp0, int Wp0, const float* src1, int N1, int Hp1, int Wp1,
+                      int rows, int h_max, int w_max, int swap_rb, void* stream);
+
 /* A training batch from uint8 images on the device: the train phase of PairedImageDataset.__getitem__ after the decode
  * (basicsr/data/paired_image_dataset.py:80-131 at scale 1) and the default collate, csrc/patch_batch.hip.h.  Per sample b the
  * row table[b] = {lq_ptr, gt_ptr, h, w, top, left, mode, reserved} (int64 each; the two pointers are device addresses of

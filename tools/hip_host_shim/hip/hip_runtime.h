@@ -1,4 +1,4 @@
-// hip_runtime.h for tools/emulate_patch_batch.cpp ONLY: just enough of the HIP kernel language to compile a kernel header for the
+// hip_runtime.h for tools/emulate_patch_batch.cpp and tools/emulate_images_io.cpp ONLY: just enough of the HIP kernel language to compile a kernel header for the
 // host - one std::thread per GPU thread, __syncthreads() a barrier over the workgroup, __shared__ a static (one workgroup at a time).
 #pragma once
 #include <stdint.h>

@@ -59,6 +59,8 @@ SIGNATURES = {
     "wm_layernorm_tok_bwd": (_i, [_p, _p, _p, _c.c_float, _p, _p, _p, _i64, _i, _p]),
     "wm_image_pre_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "wm_image_post_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "wm_images_pre_u8": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "wm_images_post_u8": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "wm_paired_patches_u8": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "wm_linear_wgrad": (_i, [_p, _p, _p, _i64, _i, _i, _p]),
     "wm_conv2d_wgrad_workspace_bytes": (_sz, [_i] * 6),

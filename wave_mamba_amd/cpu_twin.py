@@ -7,6 +7,11 @@ LOLv1 / 1x3x256x256 "CPU-only PyTorch forward (plumbing, no GPU)").
     ss2d_core           SS2D.forward_core           :446-478 (for the torch.library op wavemamba_hip::ss2d_core on CPU tensors)
     paired_patches      the train phase of PairedImageDataset.__getitem__ after the decode + default collate
                         (/root/reference/basicsr/data/paired_image_dataset.py:80-131; host form of ops.paired_patches_u8)
+    dihedral(_inverse)  the eight flips / rotations of data_augmentation (basicsr/data/transforms.py:223-268) and
+                        what undoes them, as views
+    images_pre_u8       N uint8 images, a mode each -> reflect_pad(chw(mode(img)) / 255), padded after the transform
+                        (host form of ops.images_pre_u8; inference_wavemamba.py:28-36, :99-105 on the transformed image)
+    images_post_u8      the fp32 mean of k network outputs turned back, quantised to uint8 (host form of ops.images_post_u8)
     grad_guard          gradient norm, non-finite flag and clipping divisor of the guarded optimizer step (no reference counterpart;
                         host form of ops.grad_guard)
     adamw_step          torch.optim.AdamW's single-tensor update plus the reference's model_ema (base_model.py:85-92; host form of
@@ -206,6 +211,69 @@ def paired_patches(pairs, rows, gt_size, swap_rb=True):
             out[k].append(a.permute(2, 0, 1).to(torch.float32) / 255.0)
     empty = torch.empty(0, 3, P, P, dtype=torch.float32)
     return tuple(torch.stack(o) if o else empty.clone() for o in out)
+
+
+DIHEDRAL_INVERSE = (0, 1, 6, 3, 4, 5, 2, 7)      # mode -> the mode that undoes it: the two rotations by a quarter swap
+
+
+def dihedral(img, mode, dims=(0, 1)):
+    """data_augmentation(img, mode) (transforms.py:223-268) on a tensor whose image axes are `dims` = (rows, columns) - (0, 1) for
+    (h, w, 3), (-2, -1) for (..., h, w): out[i, j] = A[r, c] by _AUG_MODES, (h, w) -> (w, h) for modes 2, 3, 6, 7.  A view."""
+    turn, flip_r, flip_c = _AUG_MODES[mode]
+    flips = [d for d, f in zip(dims, (flip_r, flip_c)) if f]
+    a = img.flip(flips) if flips else img
+    return a.transpose(*dims) if turn else a
+
+
+def dihedral_inverse(img, mode, dims=(0, 1)):
+    """The transform that undoes dihedral(., mode): dihedral(., DIHEDRAL_INVERSE[mode])."""
+    return dihedral(img, DIHEDRAL_INVERSE[mode], dims)
+
+
+def _pad_to(n, window_size):
+    return n + (window_size - n % window_size) % window_size
+
+
+def images_pre_u8(images, modes, window_size=128, swap_rb=True):
+    """ops.images_pre_u8 in plain PyTorch: per (h, w, 3) uint8 image (numpy array or CPU tensor) and mode,
+    reflect_pad(chw(dihedral(img, mode)) / 255) bottom / right to multiples of window_size - the padding follows the transform, as
+    check_image_size(aug(img)) pads - stacked to (N, 3, Hp, Wp) float32.  A padding that reaches the transformed image's size and
+    images that pad to different shapes raise RuntimeError."""
+    out = []
+    for im, mode in zip(images, modes, strict=True):
+        a = dihedral(torch.as_tensor(im), mode)
+        if a.dtype != torch.uint8 or a.dim() != 3 or a.shape[2] != 3:
+            raise RuntimeError(f"images_pre_u8: expected (h, w, 3) uint8 images, got {tuple(a.shape)} {a.dtype}")
+        h, w = a.shape[:2]
+        Hp, Wp = _pad_to(h, window_size), _pad_to(w, window_size)
+        if h < 1 or w < 1 or Hp - h >= h or Wp - w >= w:
+            raise RuntimeError(f"images_pre_u8: the reflect padding of a {h} x {w} image to {Hp} x {Wp} reaches the image's size")
+        if swap_rb:
+            a = a.flip(-1)
+        x = a.permute(2, 0, 1).to(torch.float32) / 255.0
+        out.append(F.pad(x[None], (0, Wp - w, 0, Hp - h), "reflect")[0])
+    if len({tuple(o.shape) for o in out}) > 1:
+        raise RuntimeError(f"images_pre_u8: the images pad to different shapes: {sorted({tuple(o.shape[1:]) for o in out})}")
+    return torch.stack(out)
+
+
+def images_post_u8(sources, rows, swap_rb=True):
+    """ops.images_post_u8 in plain PyTorch.  sources: one (N, 3, Hp, Wp) float32 tensor or a pair of them; rows: per destination
+    (h, w, [(tensor, index, mode), ...]) - the k network outputs of the (h, w) image transformed by `mode`.  Per destination:
+    y_s = dihedral_inverse(source cropped to the transformed shape, mode); mean = (((y_0 + y_1) + y_2) + ...) * (1 / k) in float32,
+    in the row's order; -> hwc(round_half_even(clamp(mean, 0, 1) * 255)) uint8, channels reversed with swap_rb.  A list of (h, w, 3)."""
+    sources = (sources,) if isinstance(sources, torch.Tensor) else tuple(sources)
+    out = []
+    for h, w, srcs in rows:
+        total = None
+        for which, index, mode in srcs:
+            ht, wt = (w, h) if _AUG_MODES[mode][0] else (h, w)
+            y = dihedral_inverse(sources[which][index, :, :ht, :wt].to(torch.float32), mode, (-2, -1))
+            total = y.clone() if total is None else total + y
+        mean = total * torch.tensor(1.0 / len(srcs), dtype=torch.float32)
+        q = (mean.clamp(0, 1) * 255.0).round().to(torch.uint8).permute(1, 2, 0)
+        out.append((q.flip(-1) if swap_rb else q).contiguous())
+    return out
 
 
 def grad_guard(tensors, max_norm=None):

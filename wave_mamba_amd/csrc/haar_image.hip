@@ -4,6 +4,7 @@
 #include "host_common.h"
 #include "haar.hip.h"
 #include "imageio.hip.h"
+#include "images_io.hip.h"
 #include "loss.hip.h"
 #include "metrics.hip.h"
 #include "patch_batch.hip.h"
@@ -211,6 +212,36 @@ int wm_image_post_u8(const float* in, uint8_t* image, int h, int w, int Hp, int 
     if (h > 65535) return WM_EUNSUPPORTED;
     hipLaunchKernelGGL(image_post_kernel, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, (hipStream_t)stream,
                        in, image, h, w, Hp, Wp, swap_rb);
+    return launch_status();
+}
+
+// N images per launch from a device table (csrc/images_io.hip.h).  The limits are those of the single-image kernels above and of the
+// metrics: at most 65535 rows of pixels (Hp, the largest destination's h) and 65535 images (grid.y of wm_image_pre_u8 /
+// wm_image_post_u8, grid.z of wm_psnr_ssim_y_u8), and at most 65535 * 32 columns.
+static bool io_extent_ok(int n, int rows, int cols) { return n <= 65535 && rows <= 65535 && cols <= 65535 * IO_TILE; }
+
+int wm_images_pre_u8(const int64_t* table, float* out, int N, int Hp, int Wp, int swap_rb, void* stream) {
+    if (N < 0 || Hp < 0 || Wp < 0) return WM_EINVAL;
+    if (N == 0 || Hp == 0 || Wp == 0) return WM_OK;
+    if (!table || !out) return WM_ENULL;
+    if ((reinterpret_cast<uintptr_t>(table) & 7u) || (reinterpret_cast<uintptr_t>(out) & 3u)) return WM_EALIGN;
+    if (!io_extent_ok(N, Hp, Wp)) return WM_EUNSUPPORTED;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the table's fields are read as long long");
+    hipLaunchKernelGGL(images_pre_kernel, dim3((unsigned)((Wp + IO_TILE - 1) / IO_TILE), (unsigned)((Hp + IO_TILE - 1) / IO_TILE), (unsigned)N),
+                       dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(table), out, Hp, Wp, swap_rb);
+    return launch_status();
+}
+
+int wm_images_post_u8(const int64_t* table, const float* src0, int N0, int Hp0, int Wp0, const float* src1, int N1, int Hp1, int Wp1,
+                      int rows, int h_max, int w_max, int swap_rb, void* stream) {
+    if (rows < 0 || h_max < 0 || w_max < 0 || N0 < 0 || Hp0 < 0 || Wp0 < 0 || N1 < 0 || Hp1 < 0 || Wp1 < 0) return WM_EINVAL;
+    if (rows == 0 || h_max == 0 || w_max == 0) return WM_OK;
+    if (!table || !src0 || (N1 > 0 && !src1)) return WM_ENULL;
+    if ((reinterpret_cast<uintptr_t>(table) & 7u) || ((reinterpret_cast<uintptr_t>(src0) | reinterpret_cast<uintptr_t>(src1)) & 3u)) return WM_EALIGN;
+    if (!io_extent_ok(rows, h_max, w_max)) return WM_EUNSUPPORTED;
+    const IoSource s0{src0, N0, Hp0, Wp0}, s1{N1 > 0 ? src1 : nullptr, N1, Hp1, Wp1};
+    hipLaunchKernelGGL(images_post_kernel, dim3((unsigned)((w_max + IO_TILE - 1) / IO_TILE), (unsigned)((h_max + IO_TILE - 1) / IO_TILE), (unsigned)rows),
+                       dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(table), s0, s1, swap_rb);
     return launch_status();
 }
 

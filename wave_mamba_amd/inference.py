@@ -19,9 +19,20 @@ def check_image_size(x, window_size=128):
 
 
 @torch.no_grad()
-def enhance(net, img, window_size=128):
+def enhance(net, img, window_size=128, ensemble=False):
     """img: (B, 3, h, w) float in [0, 1] on the model's device -> restored image, same shape
-    (inference_wavemamba.py:99-113: pad -> restoration_network -> crop)."""
+    (inference_wavemamba.py:99-113: pad -> restoration_network -> crop).
+    ensemble=True: the geometric self-ensemble - the mean over the eight modes m of data_augmentation (transforms.py:223-268) of
+    inverse_m(enhance(net, aug_m(img))), each transformed image padded after its transform; the sum runs in ascending mode order in
+    the image's dtype and is multiplied by 1 / 8 (cpu_twin.dihedral, the order of ops.images_post_u8)."""
+    if ensemble:
+        from . import cpu_twin
+        total = None
+        for mode in range(8):
+            turned = cpu_twin.dihedral(img, mode, (-2, -1)).contiguous()
+            y = cpu_twin.dihedral_inverse(enhance(net, turned, window_size), mode, (-2, -1))
+            total = y.clone() if total is None else total + y
+        return total * 0.125
     _, _, h, w = img.shape
     out = net.restoration_network(check_image_size(img, window_size))
     return out[:, :, :h, :w]
@@ -41,6 +52,160 @@ def psnr_uint8(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Captured forwards: below UHD the forward's kernels take less time than the host needs to launch them.
+# ------------------------------------------------------------------------------------------------------------------
+def _weights_signature(net):
+    """What a captured forward of `net` depends on beyond its input: every parameter's and buffer's address and version, and the
+    generation of the prepared weight copies (ops.conv2d_cache_clear: a write through `.data` bumps no version) - the rule of
+    ops._PreparedCache."""
+    from . import ops
+    return (ops.prepared_generation(),) + tuple((t.data_ptr(), t._version) for t in list(net.parameters()) + list(net.buffers()))
+
+
+def _capture(step, device):
+    """Run `step` once eagerly (prepared-weight caches, allocator, the forward's side streams) and capture it into a graph ->
+    (graph, step's result under capture).  The sequence of tests/test_gpu_parity.py::test_hip_graph_capture_after_a_multi_stream_forward
+    and of bench.py's graph leg, with one difference from the latter: the warm-up runs on the CURRENT stream, not on a new side
+    stream.  torch hands streams out of a pool of 32 per device, round robin, so a stream made here can carry the handle of one of
+    the side streams the forward reserves for captures (wavemamba_arch._side_streams), and every new main stream makes the
+    forward create three more.  A prepared weight copy that the warm-up produced on such a handle is then waited for, under
+    capture, through an event of a stream that is itself capturing - and the capture ends with hipErrorStreamCaptureUnjoined
+    (measured: cold caches and an aliased handle fail, warm caches or no alias pass).  On the current stream the
+    copies come from the streams an eager forward of the caller would use.  Thread-local capture mode when a process group is
+    initialised (its watchdog thread polls events while this thread captures)."""
+    import gc
+    import torch.distributed as dist
+    with torch.cuda.device(device):
+        step()
+        graph = torch.cuda.CUDAGraph()
+        mode = {"capture_error_mode": "thread_local"} if dist.is_available() and dist.is_initialized() else {}
+        torch.cuda.synchronize(device)
+        # No graph may be destroyed while this one is captured: ~CUDAGraph calls hipGraphDestroy, which a capturing stream refuses,
+        # and the error leaves a destructor - the process aborts.  Graphs that are garbage go now, and the cycle collector, which
+        # could find one in the middle of the capture (torch.cuda.graph does not collect on entry any more), rests until the end.
+        gc.collect()
+        resting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, **mode):
+                out = step()
+        finally:
+            if resting:
+                gc.enable()
+    return graph, out
+
+
+class GraphedForward:
+    """net.restoration_network as captured graphs: one per input shape (N, Hp, Wp), with a static input and a static output.
+
+        fwd = GraphedForward(net)
+        y = fwd(x)            # x: (N, 3, Hp, Wp) float32 on the net's device, Hp and Wp multiples of the window (check_image_size)
+
+    The first call with a shape runs one eager forward on the current stream and captures (_capture); later calls copy x into the static input and
+    replay - bit-equal to the eager forward.  The result is the graph's static output: it is overwritten by the next call with
+    that shape (clone it to keep it).  At most `max_shapes` graphs are kept, the least recently used leaving first - each owns a
+    private memory pool, gigabytes at 3840 x 2160.  Every graph is dropped when a parameter or buffer of the net changes its
+    address or version, or ops.conv2d_cache_clear has run (_weights_signature).  `captures` counts the captures made."""
+
+    def __init__(self, net, max_shapes=4):
+        import collections
+        if int(max_shapes) < 1:
+            raise ValueError(f"GraphedForward: max_shapes must be at least 1, got {max_shapes}")
+        self.net, self.max_shapes, self.captures = net, int(max_shapes), 0
+        self._ent = collections.OrderedDict()          # (device, N, Hp, Wp) -> (graph, static input, static output)
+        self._sig = None
+
+    def _drop(self, device, everything=False):
+        torch.cuda.synchronize(device)                 # no graph is destroyed under its own replay
+        if everything:
+            self._ent.clear()
+        else:
+            self._ent.popitem(last=False)
+
+    @torch.no_grad()
+    def __call__(self, x):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
+            raise RuntimeError("GraphedForward: expected a (N, 3, Hp, Wp) float32 CUDA tensor, got "
+                               + (f"{tuple(x.shape)} {x.dtype} on {x.device}" if isinstance(x, torch.Tensor) else type(x).__name__))
+        home = next((p.device for p in self.net.parameters()), x.device)
+        if x.device != home:
+            raise RuntimeError(f"GraphedForward: the input is on {x.device}, the network on {home}")
+        sig = _weights_signature(self.net)
+        if sig != self._sig:
+            if self._ent:
+                self._drop(x.device, everything=True)
+            self._sig = sig
+        key = (x.device, x.shape[0], x.shape[2], x.shape[3])
+        ent = self._ent.get(key)
+        if ent is None:
+            while len(self._ent) >= self.max_shapes:
+                self._drop(x.device)
+            static_in = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            static_in.copy_(x)
+            graph, out = _capture(lambda: self.net.restoration_network(static_in), x.device)
+            self.captures += 1
+            ent = self._ent[key] = (graph, static_in, out)
+        else:
+            self._ent.move_to_end(key)
+            ent[1].copy_(x)
+        ent[0].replay()
+        return ent[2]
+
+
+class _BatchPlan:
+    """What the batched UInt8Pipeline owns per (image shape, batch, slot, scored): the pinned and device staging buffers, the static
+    network inputs, the two device tables and - graphed - the captured pre -> forward -> post (-> psnr_ssim_y).  Everything a launch
+    names is allocated here, before any capture, so a graph holds no pointer that moves."""
+
+    _ENSEMBLE_MODES = ((0, 1, 4, 5), (2, 3, 6, 7))     # the shape-keeping transforms and the transposing ones: two batches
+
+    def __init__(self, pipe, h, w, B, scored, crop_border):
+        ops, dev = pipe.ops, pipe.device
+        self.B, self.scored, self.crop = B, scored, crop_border          # (no reference to `pipe`: a cycle would leave the graph to the collector)
+        shape = (B, h, w, 3)
+        self.pin_in, self.pin_out = (torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(2))
+        self.dev_in, self.res = (torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(2))
+        self.pin_tgt = torch.empty(shape, dtype=torch.uint8, pin_memory=True) if scored else None
+        self.dev_tgt = torch.empty(shape, dtype=torch.uint8, device=dev) if scored else None
+        self.pin_met = torch.empty((B, 2), dtype=torch.float64, pin_memory=True) if scored else None
+        mode_sets = self._ENSEMBLE_MODES if pipe.ensemble else ((0,),)
+        self.pre, where = [], {}
+        for which, modes in enumerate(mode_sets):
+            table, _ = ops.images_io_table(pre=[(self.dev_in[b], m) for b in range(B) for m in modes], window_size=pipe.window)
+            self.pre.append((table, torch.empty((table.n, 3, table.H, table.W), dtype=torch.float32, device=dev)))
+            for b in range(B):
+                for at, m in enumerate(modes):
+                    where[b, m] = (which, len(modes) * b + at, m)
+        modes = sorted(m for ms in mode_sets for m in ms)                      # the sum runs in ascending mode order
+        _, self.post = ops.images_io_table(post=[(self.res[b], [where[b, m] for m in modes]) for b in range(B)])
+        self.up_done = self.consumed = self.dl_done = None
+        self.graph = self.met = self.signature = None
+
+    def _step(self, pipe):
+        ops = pipe.ops
+        ys = [pipe.net.restoration_network(ops.images_pre_u8(t, t.n, t.H, t.W, pipe.swap_rb, out=x)) for t, x in self.pre]
+        ops.images_post_u8(self.post, ys, pipe.swap_rb)
+        if not self.scored:
+            return None
+        return ops.psnr_ssim_y(self.res, self.dev_tgt, self.crop, layout="HWC", bgr=pipe.swap_rb)
+
+    def launch(self, pipe):
+        """pre -> forward(s) -> post (-> metrics) on the current stream, eagerly or as one replay -> the (B, 2) metrics or None."""
+        if not pipe.graphed:
+            return self._step(pipe)
+        sig = _weights_signature(pipe.net)
+        if self.graph is None or sig != self.signature:
+            if self.graph is not None:
+                torch.cuda.synchronize(pipe.device)
+                self.graph = self.met = None
+            self.graph, self.met = _capture(lambda: self._step(pipe), pipe.device)
+            self.signature = sig
+            pipe.captures += 1
+        self.graph.replay()
+        return self.met
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # uint8 host images in, uint8 host images out (inference_wavemamba.py:99-113 end to end, SURVEY 8f rank 3):
 # pinned double-buffered H2D / D2H on side streams under the previous / next image's forward.
 # ------------------------------------------------------------------------------------------------------------------
@@ -55,11 +220,30 @@ class UInt8Pipeline:
     `run(images, targets)` also scores every result against its ground truth (host uint8, same shape) on the device, as the
     reference's evaluation loop does (inference_wavemamba.py:116-117: Y-channel PSNR / SSIM, crop_border 1): the target travels
     with its input on the upload stream, ops.psnr_ssim_y reads the device result before the download, and the two doubles come
-    back with the image's copy.  It then yields (image, psnr, ssim)."""
+    back with the image's copy.  It then yields (image, psnr, ssim).
 
-    def __init__(self, net, device, window_size=128, swap_rb=True):
+    Three opt-in switches, for images below UHD, where the forward's kernels take less time than the host needs to launch them
+    (profiles/inference_pipeline/README.md); with none given every call launches what is described above:
+      batch > 1      consecutive images of equal shape are enhanced in one forward (wm_images_pre_u8 / wm_images_post_u8, N images
+                     per launch); a change of shape or the end of the input flushes a short batch;
+      ensemble=True  geometric self-ensemble: per image the eight transforms of data_augmentation as two forwards of four (the
+                     shape-keeping modes 0, 1, 4, 5 and the transposing 2, 3, 6, 7; of 4 * batch with batch > 1), turned back and
+                     averaged in fp32 in ascending mode order before the quantisation;
+      graphed=True   pre -> forward -> post (-> psnr_ssim_y) replay from a captured graph per (image shape, batch, slot); a graph is
+                     dropped when a weight changes (GraphedForward's rule).  `captures` counts the captures made.
+    In these modes a step's buffers and device tables live in a _BatchPlan per (shape, batch, slot) - at most `max_plans`, the least
+    recently used leaving first; the two slots, the two side streams and their events work as above.  Graphed, every plan owns
+    its graph and the graph its private memory pool - a whole forward's intermediates, gigabytes at 3840 x 2160 - so one image shape
+    costs two such pools (one per slot), a short last batch two more: lower `max_plans` (at least 2) where memory is short."""
+
+    def __init__(self, net, device, window_size=128, swap_rb=True, batch=1, ensemble=False, graphed=False, max_plans=8):
         from . import ops
+        import collections
+        if int(batch) < 1 or int(max_plans) < 2:
+            raise ValueError(f"UInt8Pipeline: batch must be at least 1 and max_plans at least 2, got {batch} and {max_plans}")
         self.net, self.device, self.window, self.swap_rb, self.ops = net, torch.device(device), window_size, swap_rb, ops
+        self.batch, self.ensemble, self.graphed, self.max_plans, self.captures = int(batch), bool(ensemble), bool(graphed), int(max_plans), 0
+        self._plans = collections.OrderedDict()         # (h, w, B, slot, scored, crop_border) -> _BatchPlan
         self.up, self.down = torch.cuda.Stream(self.device), torch.cuda.Stream(self.device)
         self._pin_in, self._pin_out, self._dev_in = [None, None], [None, None], [None, None]
         self._pin_tgt, self._dev_tgt, self._pin_met = [None, None], [None, None], [None, None]   # run(images, targets) only
@@ -78,6 +262,9 @@ class UInt8Pipeline:
     @torch.no_grad()
     def run(self, images, targets=None, crop_border=1):
         import numpy as np
+        if self.batch > 1 or self.ensemble or self.graphed:
+            yield from self._run_batched(images, targets, crop_border)
+            return
         main = torch.cuda.current_stream(self.device)
         pending = []                                   # (pinned output, pinned metrics or None, download-done event)
         uploaded = None
@@ -163,6 +350,111 @@ class UInt8Pipeline:
         for p in pending:
             yield self._hand_out(*p)
 
+    def _groups(self, items, scored):
+        """Consecutive (image, target) items of equal shape, at most `batch` at a time, as lists of contiguous uint8 arrays."""
+        import numpy as np
+        group = []
+        for item in items:
+            img, tgt = item if scored else (item, None)
+            a = np.ascontiguousarray(img)
+            t = None if tgt is None else np.ascontiguousarray(tgt, dtype=np.uint8)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"UInt8Pipeline.run: expected (h, w, 3) uint8 images, got {a.shape} {a.dtype}")
+            if t is not None and t.shape != a.shape:
+                raise ValueError(f"UInt8Pipeline.run: target shape {t.shape} != image shape {a.shape}")
+            if group and group[0][0].shape != a.shape:
+                yield group
+                group = []
+            group.append((a, t))
+            if len(group) == self.batch:
+                yield group
+                group = []
+        if group:
+            yield group
+
+    def _plan(self, key):
+        plan = self._plans.get(key)
+        if plan is None:
+            while len(self._plans) >= self.max_plans:
+                torch.cuda.synchronize(self.device)    # nothing of a plan is freed under a copy or a replay that uses it
+                self._plans.popitem(last=False)
+            plan = self._plans[key] = _BatchPlan(self, *key[:3], *key[4:])
+        else:
+            self._plans.move_to_end(key)
+        return plan
+
+    def _run_batched(self, images, targets, crop_border):
+        """run() with batch > 1, ensemble or graphed: the loop of run() over groups of images, a _BatchPlan per group."""
+        main = torch.cuda.current_stream(self.device)
+        scored = targets is not None
+        groups = self._groups(iter(images) if not scored else zip(images, targets, strict=True), scored)
+        pending = []                                   # (plan, images in it, download-done event)
+
+        def upload(group, slot):
+            """Stage a group into its plan: host -> pinned -> device on the upload stream, with run()'s orderings - the host refills
+            the pinned buffers only after the previous copies out of them, the copies into the device buffers wait for main's last
+            launch that read them (for main itself on the first use: the plan's memory is main's)."""
+            h, w = group[0][0].shape[:2]
+            with torch.cuda.device(self.device):
+                plan = self._plan((h, w, len(group), slot, scored, crop_border))
+            if plan.up_done is not None:
+                plan.up_done.synchronize()
+            for b, (a, t) in enumerate(group):
+                plan.pin_in[b].copy_(torch.from_numpy(a))
+                if t is not None:
+                    plan.pin_tgt[b].copy_(torch.from_numpy(t))
+            with torch.cuda.stream(self.up):
+                if plan.consumed is not None:
+                    self.up.wait_event(plan.consumed)
+                else:
+                    self.up.wait_stream(main)
+                plan.dev_in.copy_(plan.pin_in, non_blocking=True)
+                if scored:
+                    plan.dev_tgt.copy_(plan.pin_tgt, non_blocking=True)
+                ev = torch.cuda.Event(); ev.record(self.up)
+            plan.up_done = ev
+            return plan, len(group)
+
+        slot = 0
+        nxt = next(groups, None)
+        staged = upload(nxt, slot) if nxt is not None else None
+        while staged is not None:
+            plan, count = staged
+            nxt = next(groups, None)
+            staged = upload(nxt, slot ^ 1) if nxt is not None else None       # overlaps with the forward below
+            main.wait_event(plan.up_done)
+            if plan.dl_done is not None:
+                main.wait_event(plan.dl_done)          # the plan's previous results have left res (and the graph's metrics)
+            met = plan.launch(self)
+            c = torch.cuda.Event(); c.record(main)
+            plan.consumed = c                          # dev_in and dev_tgt may be overwritten by the upload stream after this
+            with torch.cuda.stream(self.down):
+                self.down.wait_event(c)
+                plan.pin_out.copy_(plan.res, non_blocking=True)
+                if met is not None:
+                    plan.pin_met.copy_(met, non_blocking=True)
+                    if not self.graphed:
+                        met.record_stream(self.down)
+                dl = torch.cuda.Event(); dl.record(self.down)
+            plan.dl_done = dl
+            pending.append((plan, count, dl))
+            if len(pending) == 2:                      # the slot about to be reused must have been handed out
+                yield from self._hand_out_group(*pending.pop(0))
+            slot ^= 1
+        for p in pending:
+            yield from self._hand_out_group(*p)
+
+    @staticmethod
+    def _hand_out_group(plan, count, done):
+        done.synchronize()
+        for b in range(count):
+            img = plan.pin_out[b].numpy().copy()
+            if plan.pin_met is None:
+                yield img
+            else:
+                psnr, ssim = plan.pin_met[b].tolist()
+                yield img, psnr, ssim
+
     @staticmethod
     def _hand_out(pin_out, pin_met, done):
         done.synchronize()
@@ -173,13 +465,15 @@ class UInt8Pipeline:
         return img, psnr, ssim
 
 
-def evaluate(net, device, images, targets, crop_border=1, swap_rb=True):
+def evaluate(net, device, images, targets, crop_border=1, swap_rb=True, batch=1, ensemble=False, graphed=False):
     """The reference's evaluation loop (inference_wavemamba.py:99-135) on host uint8 images (BGR, as cv2 reads them; RGB with
     swap_rb=False) and their ground truths: enhance every image on `device` (UInt8Pipeline) and score it on the device with
     the Y-channel PSNR / SSIM of comput_psnr_ssim.py (metrics.py).  LPIPS (:118-123) is not computed.
+    batch, ensemble, graphed: UInt8Pipeline's switches (images per forward, geometric self-ensemble, graph replay).
     -> {"psnr": [...], "ssim": [...], "avg_psnr": mean, "avg_ssim": mean} (the averages :133-134 print)."""
     psnr, ssim = [], []
-    for _, p, s in UInt8Pipeline(net, device, swap_rb=swap_rb).run(images, targets, crop_border):
+    pipe = UInt8Pipeline(net, device, swap_rb=swap_rb, batch=batch, ensemble=ensemble, graphed=graphed)
+    for _, p, s in pipe.run(images, targets, crop_border):
         psnr.append(p)
         ssim.append(s)
     n = max(len(psnr), 1)

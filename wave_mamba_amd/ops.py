@@ -1091,6 +1091,144 @@ def image_post_u8(t, h, w, swap_rb=True):
     return out
 
 
+IMAGES_IO_TILE = 32                        # csrc/images_io.hip.h: IO_TILE - one workgroup per 32 x 32 tile (the tests' edge shapes)
+IMAGES_PRE_WORDS, IMAGES_POST_WORDS = 4, 12      # IO_PRE_WORDS, IO_POST_WORDS: int64 per row
+_IMAGES_TURN = (False, False, True, True, False, False, True, True)    # modes 2, 3, 6, 7 turn (h, w) into (w, h)
+
+
+class ImagesTable:
+    """One device table of images_io_table: `rows` (n, words) int64 on the device; pre: the padded shape (H, W) every row gives;
+    post: the largest destination (H, W) and, per source tensor, (images, rows, columns) it must at least hold (`need`).
+    `keep` holds the tensors whose addresses the table names, so they live as long as the table does."""
+
+    def __init__(self, kind, rows, n, H, W, need, keep):
+        self.kind, self.rows, self.n, self.H, self.W, self.need, self.keep = kind, rows, n, H, W, need, keep
+
+
+def _images_u8(name, t, dev):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 and t.is_contiguous()):
+        what = f"{tuple(t.shape)} {t.dtype} on {t.device}, contiguous: {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"images_io_table: {name} must be a contiguous (h, w, 3) uint8 CUDA tensor, got {what}")
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise RuntimeError(f"images_io_table: {name} is empty: {tuple(t.shape)}")
+    if dev is not None and t.device != dev:
+        raise RuntimeError(f"images_io_table: the images live on more than one device ({dev}, {t.device})")
+    return t.device
+
+
+def images_io_table(pre=None, post=None, window_size=128):
+    """The device tables wm_images_pre_u8 and wm_images_post_u8 read (include/wavemamba_hip.h) -> (pre table, post table), each
+    an ImagesTable, or None for a list not given.
+    pre: [(image, mode), ...] - contiguous (h, w, 3) uint8 CUDA images and modes 0..7 of data_augmentation; image n of the launch's
+    output is reflect_pad(chw(mode(image)) / 255), padded bottom / right to multiples of window_size AFTER the transform.  Every row
+    must pad to the same (Hp, Wp), and a padding that reaches the transformed image's size raises RuntimeError, as F.pad(...,
+    'reflect') does.
+    post: [(image, [(tensor, index, mode), ...]), ...] - contiguous (h, w, 3) uint8 CUDA destinations, each the mean of k = 1 or 8
+    sources in the order given: image `index` of source tensor 0 or 1 of the launch, which holds the network's result on the
+    destination-shaped image transformed by `mode`.
+    Like grad_guard_table the tables are built OUTSIDE a graph capture (RuntimeError inside one) and hold raw addresses: the images
+    are kept alive by the table (ImagesTable.keep) and must stay in place, and a graph that captured a launch on a table needs the
+    table for as long as it is replayed."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("images_io_table: a host-to-device copy must not be captured - build the tables before the capture")
+    window = int(window_size)
+    if window < 1:
+        raise RuntimeError(f"images_io_table: window_size must be positive, got {window_size}")
+    dev = None
+    pre_rows, post_rows, shapes = [], [], set()
+    for n, (img, mode) in enumerate(pre or ()):
+        dev = _images_u8(f"pre image {n}", img, dev)
+        if not (isinstance(mode, int) and 0 <= mode <= 7):
+            raise RuntimeError(f"images_io_table: pre row {n}: mode must be 0..7, got {mode!r}")
+        h, w = img.shape[:2]
+        ht, wt = (w, h) if _IMAGES_TURN[mode] else (h, w)
+        Hp, Wp = ht + (window - ht % window) % window, wt + (window - wt % window) % window
+        if Hp - ht >= ht or Wp - wt >= wt:
+            raise RuntimeError(f"images_io_table: pre row {n}: the reflect padding of a {ht} x {wt} image (mode {mode}) to {Hp} x {Wp} "
+                               "reaches the image's size")
+        shapes.add((Hp, Wp))
+        pre_rows.append((img.data_ptr(), h, w, mode))
+    if len(shapes) > 1:
+        raise RuntimeError(f"images_io_table: the pre rows pad to different shapes {sorted(shapes)}: one launch writes one (N, 3, Hp, Wp)")
+    need = [[0, 0, 0], [0, 0, 0]]
+    hmax = wmax = 0
+    for n, (img, srcs) in enumerate(post or ()):
+        dev = _images_u8(f"post image {n}", img, dev)
+        srcs = list(srcs)
+        if len(srcs) not in (1, 8):
+            raise RuntimeError(f"images_io_table: post row {n}: 1 or 8 sources, got {len(srcs)}")
+        h, w = img.shape[:2]
+        hmax, wmax = max(hmax, h), max(wmax, w)
+        words = []
+        for which, index, mode in srcs:
+            if which not in (0, 1) or not (isinstance(mode, int) and 0 <= mode <= 7) or not 0 <= index < (1 << 31):
+                raise RuntimeError(f"images_io_table: post row {n}: a source is (tensor 0 or 1, index >= 0, mode 0..7), got {(which, index, mode)}")
+            ht, wt = (w, h) if _IMAGES_TURN[mode] else (h, w)
+            need[which] = [max(need[which][0], index + 1), max(need[which][1], ht), max(need[which][2], wt)]
+            words.append(mode | which << 8 | index << 16)
+        post_rows.append((img.data_ptr(), h, w, len(srcs)) + tuple(words) + (0,) * (8 - len(words)))
+    up = _GUARD_UPLOADS.setdefault(dev.index, _GuardTableUpload()) if dev is not None else None
+    pre_t = post_t = None
+    if pre is not None:
+        rows = up.upload(pre_rows, dev) if pre_rows else torch.empty((0, IMAGES_PRE_WORDS), dtype=torch.int64, device=dev or "cuda")
+        Hp, Wp = next(iter(shapes)) if shapes else (0, 0)
+        pre_t = ImagesTable("pre", rows, len(pre_rows), Hp, Wp, None, [img for img, _ in pre])
+    if post is not None:
+        rows = up.upload(post_rows, dev) if post_rows else torch.empty((0, IMAGES_POST_WORDS), dtype=torch.int64, device=dev or "cuda")
+        post_t = ImagesTable("post", rows, len(post_rows), hmax, wmax, need, [img for img, _ in post])
+    return pre_t, post_t
+
+
+def images_pre_u8(table, N, Hp, Wp, swap_rb=True, out=None):
+    """N uint8 device images -> (N, 3, Hp, Wp) fp32 in [0, 1] in one launch (wm_images_pre_u8): image n is the table's row n
+    transformed by its mode, channel-major, / 255, reflect-padded after the transform; swap_rb: BGR -> RGB.  `table`: the pre table of
+    images_io_table, whose rows give this N and (Hp, Wp).  `out`: a contiguous (N, 3, Hp, Wp) float32 tensor on the table's device
+    to write into (a captured graph's static input), else a new one.  cpu_twin.images_pre_u8 states the same in plain PyTorch."""
+    if not isinstance(table, ImagesTable) or table.kind != "pre":
+        raise RuntimeError("images_pre_u8: expected the pre table of images_io_table")
+    if (table.n, table.H, table.W) != (int(N), int(Hp), int(Wp)):
+        raise RuntimeError(f"images_pre_u8: the table holds {table.n} images padded to {table.H} x {table.W}, not {N} of {Hp} x {Wp}")
+    dev = table.rows.device
+    if out is None:
+        out = torch.empty((table.n, 3, table.H, table.W), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev
+          or tuple(out.shape) != (table.n, 3, table.H, table.W) or not out.is_contiguous()):
+        raise RuntimeError(f"images_pre_u8: out must be a contiguous ({table.n}, 3, {table.H}, {table.W}) float32 tensor on {dev}, got "
+                           + (f"{tuple(out.shape)} {out.dtype} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__))
+    _launch(dev, "wm_images_pre_u8", table.rows, out, table.n, table.H, table.W, int(bool(swap_rb)))
+    return out
+
+
+def images_post_u8(table, sources, swap_rb=True):
+    """fp32 network outputs -> the table's uint8 destinations in one launch (wm_images_post_u8): per destination the fp32 mean of
+    its k sources, each cropped to its transformed shape and turned back, summed in the row's order and times 1 / k; then clamp
+    [0, 1], * 255, round half to even, channel-last; swap_rb: RGB -> BGR.  `table`: the post table of images_io_table; `sources`: one
+    contiguous (N, 3, Hp, Wp) float32 CUDA tensor or a pair of them (tensor 0 and tensor 1 of the table's source triples).
+    -> the destination images (the tensors the table was built on).  cpu_twin.images_post_u8 states the same in plain PyTorch."""
+    if not isinstance(table, ImagesTable) or table.kind != "post":
+        raise RuntimeError("images_post_u8: expected the post table of images_io_table")
+    sources = (sources,) if isinstance(sources, torch.Tensor) else tuple(sources)
+    if not 1 <= len(sources) <= 2:
+        raise RuntimeError(f"images_post_u8: one or two source tensors, got {len(sources)}")
+    _require_cuda("images_post_u8", *sources)
+    dev = table.rows.device
+    for i, t in enumerate(sources):
+        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3 or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"images_post_u8: source {i} must be a contiguous (N, 3, Hp, Wp) float32 tensor on {dev}, got "
+                               f"{tuple(t.shape)} {t.dtype} on {t.device}")
+    for i, (n, hn, wn) in enumerate(table.need):
+        have = (sources[i].shape[0], sources[i].shape[2], sources[i].shape[3]) if i < len(sources) else (0, 0, 0)
+        if n > have[0] or hn > have[1] or wn > have[2]:
+            raise RuntimeError(f"images_post_u8: the table reads {n} images of at least {hn} x {wn} from source {i}, which "
+                               + (f"is {tuple(sources[i].shape)}" if i < len(sources) else "was not given"))
+    s0 = sources[0]
+    s1 = sources[1] if len(sources) == 2 else None
+    _launch(dev, "wm_images_post_u8", table.rows, s0, s0.shape[0], s0.shape[2], s0.shape[3],
+            s1, 0 if s1 is None else s1.shape[0], 0 if s1 is None else s1.shape[2], 0 if s1 is None else s1.shape[3],
+            table.n, table.H, table.W, int(bool(swap_rb)))
+    return list(table.keep)
+
+
 def paired_patches_u8(table, P, swap_rb=True, out=None):
     """A training batch from uint8 images resident on the device (wm_paired_patches_u8, include/wavemamba_hip.h): what the
     reference's PairedImageDataset train phase and default collate produce at scale 1, bit for bit, in one launch.
@@ -1244,11 +1382,21 @@ def conv2d_select(mode=CONV3X3_AUTO):
     check(_lib.load().wm_conv2d_select(int(mode)), "wm_conv2d_select")
 
 
+_PREPARED_GENERATION = [0]
+
+
+def prepared_generation():
+    """How often conv2d_cache_clear has run: a graph captured at another count replays prepared weight copies that are gone."""
+    return _PREPARED_GENERATION[0]
+
+
 def conv2d_cache_clear():
     """Drop every prepared (bf16-split) weight copy.  The cache validates an entry by (object, data_ptr, _version); a
     write through `.data` (p.data.copy_(), basicsr-style EMA `.data.mul_().add_()`, weight surgery) does NOT bump the
     version counter, so code that updates weights that way must call this (WaveMamba.train() / .eval() / ._apply() and
-    trainer.load_network do)."""
+    trainer.load_network do).  A captured forward holds the addresses of the copies it was captured with: every call here advances
+    prepared_generation(), by which inference.GraphedForward and the graphed UInt8Pipeline drop their graphs."""
+    _PREPARED_GENERATION[0] += 1
     _WFRAG_CACHE.clear()
     _CORE_PREP_CACHE.clear()                 # (the SS2D core's prepared parameters: same validation, same caveat)
 
@@ -1779,7 +1927,7 @@ GRAD_GUARD_CHUNK = 4096                    # csrc/grad_guard.hip.h: kGuardChunk 
 
 
 class _GuardTableUpload:
-    """The two pinned slots (an event each) behind grad_guard_table and adamw_table, per device: PairedPatchBatcher's discipline - the host rewrites
+    """The two pinned slots (an event each) behind grad_guard_table, adamw_table and images_io_table, per device: PairedPatchBatcher's discipline - the host rewrites
     a slot only after the copy out of it has finished, so building the next step's table does not wait for this step's copy."""
 
     def __init__(self):
@@ -1790,7 +1938,7 @@ class _GuardTableUpload:
         self.slot ^= 1
         if self.copied[slot] is not None:
             self.copied[slot].synchronize()                        # the last copy out of this pinned slot
-        width = len(rows[0])                                       # int64 words per row: 2 (grad_guard_table), 6 (adamw_table)
+        width = len(rows[0])                                       # int64 words per row: 2 (grad_guard_table), 6 (adamw_table), 4 and 12 (images_io_table)
         words = len(rows) * width
         pin = self.pin[slot]
         if pin is None or pin.numel() < words:
